@@ -12,8 +12,13 @@ Launch: `python bench.py [--gpus N --steps K --warmup W]`.  For N>1 it either ru
 torch.distributed.run (RANK/WORLD_SIZE set) or starts the N rank processes itself
 (launch_ranks; one process per GPU, RCCL).  Pairs are sharded across ranks with no data-path collective
 (weak scaling); one all_gather of a per-rank metrics record at the end.  Rank 0 prints ONE
-JSON line.  `roofline` is measured live (HIP events on the launch stream) for the dominant
-HIP kernel; `cpu_baseline` times the CPU oracle (port of the reference path) on one pair.
+JSON line: the headline (`value`, `ms_per_step` of the K timed steps) and its configuration.
+`--dump-outputs DIR` also writes the last timed step's disparity as DIR/disp.npy.
+
+`--full` adds the secondary legs to that line, each measured after the timed steps: `roofline` /
+`kernels` live (HIP events on the launch stream) for the step's HIP kernels, `epe_vs_ref` (pair 0
+of every rank against the CPU oracle) and `cpu_baseline`, which times the CPU oracle (port of
+the reference path) on a sample of the batch's pairs.
 """
 import argparse
 import json
@@ -52,8 +57,14 @@ def parse():
     ap.add_argument("--no-graph", action="store_true", help="time eager launches, not a HIP graph")
     ap.add_argument("--graph", action="store_true",
                     help="time the HIP-graph replay even when eager launches probe faster")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--kernel-iters", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary legs of the headline line: "
+                         "parity against the CPU oracle (epe_vs_ref), per-kernel rooflines and the "
+                         "CPU baseline (a plain run times the steps and prints the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--kernel-iters", type=int, default=50, help="--full: launches per roofline timing")
     ap.add_argument("--features", default="randn", choices=sorted(FEATURE_KINDS),
                     help="synthetic feature variant (SURVEY.md §8d)")
     ap.add_argument("--train", action="store_true",
@@ -510,6 +521,52 @@ def launch_ranks(n, argv):
     return rc
 
 
+def dump_outputs(args, rank, **arrays):
+    """--dump-outputs DIR: what the last timed step returned to its caller, one DIR/<name>.npy
+    per array (float32; rank r > 0 writes <name>_rank<r>.npy).  Weights and inputs are seeded, so
+    two builds run with the same arguments can be compared array for array."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
+        assert a.nbytes <= 64 << 20, (name, a.nbytes)  # the largest here is 8x384x1248 (15 MB)
+        np.save(os.path.join(args.dump_outputs, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
+def full_legs(args, model, left, right, summary, records, world):
+    """--full: the secondary keys of the headline line, measured after the timed steps -- the live
+    per-kernel rooflines, the parity of every rank's pair 0 against the CPU oracle, and (N=1) the
+    CPU baseline."""
+    roof = kernel_rooflines(model, left, right, args.batch, args.kernel_iters)
+    # the dominant kernel of the timed C2 step (the C5 concat line is a separate config)
+    dom_name = max((k for k in roof if roof[k].get("in_step", True)), key=lambda k: roof[k]["ms"])
+    dom = roof[dom_name]
+    traffic = load_traffic(dom_name)
+    legs = {
+        "roofline": {"kernel": dom_name, "bound": dom["bound"], "achieved": dom["achieved"],
+                     "peak": dom["peak"], "unit": dom["unit"], "frac": dom["frac"],
+                     "traffic": traffic, "ms_per_launch": dom["ms"],
+                     "algorithmic_per_launch": dom["algo"],
+                     "peak_basis": peak_basis(dom),
+                     **({"gather": dom["gather"]} if "gather" in dom else {})},
+        "kernels": {k: {kk: v[kk] for kk in ("bound", "ms", "achieved", "unit", "frac", "gather",
+                                             "pairs", "bytes_per_pair", "store_ceiling_GBps",
+                                             "frac_of_store_ceiling")
+                        if kk in v}
+                    for k, v in roof.items()},
+        # EPE vs ref: mean / max |dd| of every rank's pair 0 against the CPU oracle
+        "epe_vs_ref": summary["epe"],
+        "max_abs_disp_err_vs_ref": summary["max_abs_err"],
+        "parity_pairs": len(records),
+        "per_rank": [{"pairs": r[0], "elapsed_s": r[1], "max_abs_err": r[3]}
+                     for r in records.tolist()],
+    }
+    if not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N=1 figure only
+        legs["cpu_baseline"] = cpu_baseline(model, left, right)
+    return legs
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -555,23 +612,21 @@ def main():
 
     out, elapsed, graph = timed_run(step, args, world)
     disp = out  # graph output buffer (or last eager output)
+    dump_outputs(args, rank, disp=disp)
 
-    # per-rank parity payload (this rank's pair 0 vs the CPU oracle), outside the timed region
-    sum_err, max_err, n_px, _ = parity_vs_oracle(model, left, right, disp)
+    # --full: per-rank parity payload (this rank's pair 0 vs the CPU oracle), outside the timed region
+    parity = {}
+    if args.full:
+        sum_err, max_err, n_px, _ = parity_vs_oracle(model, left, right, disp)
+        parity = dict(sum_abs_err=sum_err, max_abs_err=max_err, n_px=n_px)
     from aanet_amd import dist as adist
     record = adist.make_record(device, pairs=args.batch * args.steps, elapsed_s=elapsed,
-                               sum_abs_err=sum_err, max_abs_err=max_err, n_px=n_px,
-                               disp_min=float(disp.min()), disp_max=float(disp.max()))
+                               disp_min=float(disp.min()), disp_max=float(disp.max()), **parity)
     records = adist.gather_records(record)  # the one collective (metrics only)
     summary = adist.summarize(records)
     total_pairs, t_max = summary["pairs"], summary["elapsed_max_s"]
 
     if rank == 0:
-        roof = kernel_rooflines(model, left, right, args.batch, args.kernel_iters)
-        # the dominant kernel of the timed C2 step (the C5 concat line is a separate config)
-        dom_name = max((k for k in roof if roof[k].get("in_step", True)), key=lambda k: roof[k]["ms"])
-        dom = roof[dom_name]
-        traffic = load_traffic(dom_name)
         line = {
             "metric": METRIC,
             "value": total_pairs / t_max,
@@ -597,26 +652,11 @@ def main():
                 "hip_graph": graph is not None, "schedule": getattr(args, "schedule", None),
                 **({"options": parse_options(args.option)} if args.option else {}),
             },
-            "roofline": {"kernel": dom_name, "bound": dom["bound"], "achieved": dom["achieved"],
-                         "peak": dom["peak"], "unit": dom["unit"], "frac": dom["frac"],
-                         "traffic": traffic, "ms_per_launch": dom["ms"],
-                         "algorithmic_per_launch": dom["algo"],
-                         "peak_basis": peak_basis(dom),
-                         **({"gather": dom["gather"]} if "gather" in dom else {})},
-            "kernels": {k: {kk: v[kk] for kk in ("bound", "ms", "achieved", "unit", "frac", "gather",
-                                                 "pairs", "bytes_per_pair", "store_ceiling_GBps",
-                                                 "frac_of_store_ceiling")
-                            if kk in v}
-                        for k, v in roof.items()},
-            # EPE vs ref: mean / max |dd| of every rank's pair 0 against the CPU oracle
-            "epe_vs_ref": summary["epe"],
-            "max_abs_disp_err_vs_ref": summary["max_abs_err"],
-            "parity_pairs": len(records),
-            "per_rank": [{"pairs": r[0], "elapsed_s": r[1], "max_abs_err": r[3]}
-                         for r in records.tolist()],
         }
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N=1 figure only
-            line["cpu_baseline"] = cpu_baseline(model, left, right)
+        if args.full:
+            line.update(full_legs(args, model, left, right, summary, records, world))
+        else:
+            line["per_rank"] = [{"pairs": r[0], "elapsed_s": r[1]} for r in records.tolist()]
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
@@ -777,6 +817,7 @@ def model_main(args, device, rank, world):
             return model(left, right)[-1]
 
     out, elapsed, graph = timed_run(step, args, world)
+    dump_outputs(args, rank, disp=out)
     from aanet_amd import dist as adist
     rec = adist.make_record(device, pairs=args.batch * args.steps, elapsed_s=elapsed,
                             disp_min=float(out.min()), disp_max=float(out.max()))
@@ -847,6 +888,7 @@ def train_main(args, device, rank, world):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    dump_outputs(args, rank, loss=torch.as_tensor(loss).reshape(1))
     from aanet_amd import dist as adist
     rec = adist.make_record(device, pairs=args.train_batch * args.steps, elapsed_s=elapsed)
     summary = adist.summarize(adist.gather_records(rec))

@@ -8,8 +8,8 @@ export PYTHONUNBUFFERED=1
 for i in 1 2 3; do
   for v in new old; do
     if [ $v = old ]; then export AANET_MI355X_LIB=$PWD/abl/libold.so; else unset AANET_MI355X_LIB; fi
-    timeout -k 10 200 python bench.py --steps 50 --warmup 5 --no-cpu-baseline > gpurun_out/ab_$v.json 2>/dev/null || exit 4
-    python -c "import json; d=json.loads(open('gpurun_out/ab_$v.json').read().strip().splitlines()[-1]); k=d['kernels']; print('$v', round(d['ms_per_step'],4), 'dcn', round(k['mdcn_pw_s0']['ms']*1e3,1), 'heads', round(k['s2_heads_s0']['ms']*1e3,1), 'g3', round(k['offset_conv_s0']['ms']*1e3,1), 'tail', round(k['conv3x3_pw_s0']['ms']*1e3,1))"
+    BENCH=$(set -o pipefail; timeout -k 10 200 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1) || exit 4
+    python -c "import json, sys; d=json.loads(sys.argv[1]); k=d['kernels']; print('$v', round(d['ms_per_step'],4), 'dcn', round(k['mdcn_pw_s0']['ms']*1e3,1), 'heads', round(k['s2_heads_s0']['ms']*1e3,1), 'g3', round(k['offset_conv_s0']['ms']*1e3,1), 'tail', round(k['conv3x3_pw_s0']['ms']*1e3,1))" "$BENCH"
   done
 done
 unset AANET_MI355X_LIB

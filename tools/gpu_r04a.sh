@@ -11,6 +11,6 @@ rc=$?; tail -15 gpurun_out/pytest_gpu.log; [ $rc -le 1 ] || exit $rc
 timeout -k 10 180 python -u tools/diag_psmnet_stages.py > gpurun_out/diag_psm.log 2>&1 || { tail -20 gpurun_out/diag_psm.log; exit 3; }
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/smoke.log 2>&1 || { tail -20 gpurun_out/smoke.log; exit 4; }
 tail -1 gpurun_out/smoke.log
-timeout -k 10 400 python bench.py > gpurun_out/bench_full.json 2>&1 || exit 5
-python -c "import json; d=json.loads(open('gpurun_out/bench_full.json').read().strip().splitlines()[-1]); print('bench', round(d['value'],1), 'pairs/s', round(d['ms_per_step'],4), 'ms', d['config']['schedule'], 'roof', d['roofline']['kernel'], round(d['roofline']['frac'],3), 'epe', d['epe_vs_ref'])"
+BENCH=$(set -o pipefail; timeout -k 10 600 python bench.py --full | tail -1) || exit 5
+python -c "import json, sys; d=json.loads(sys.argv[1]); print('bench', round(d['value'],1), 'pairs/s', round(d['ms_per_step'],4), 'ms', d['config']['schedule'], 'roof', d['roofline']['kernel'], round(d['roofline']['frac'],3), 'epe', d['epe_vs_ref'])" "$BENCH"
 exit $rc

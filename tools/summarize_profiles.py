@@ -35,7 +35,7 @@ KMAP = {"corr_volume_s0": r"corr_reg_kernel<5, 8, 2>", "disp_regress_s0": r"disp
 # 1. kernel stats of the bench command
 stats = list(csv.DictReader(open(os.path.join(src, "trace", "bench_kernel_stats.csv"))))
 tot = sum(float(r["TotalDurationNs"]) for r in stats)
-lines = [f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline ({tag})",
+lines = [f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ({tag})",
          f"# total GPU kernel time {tot / 1e6:.3f} ms over the whole run (warmup, graph capture, timed steps, roofline loops)",
          f"{'total_ms':>10} {'calls':>6} {'avg_us':>9} {'pct':>6}  kernel"]
 for r in sorted(stats, key=lambda r: -float(r["TotalDurationNs"])):
