@@ -391,6 +391,9 @@ int aanet_conv3x3s2_terms_f32(const float *x, const void *wsplit, const float *b
   const bool has_terms = terms && (terms->identity || terms->up);
   if (has_terms && co_a == 0) return AANET_EINVAL;
   if (terms && terms->up && (terms->up_h <= 0 || terms->up_w <= 0)) return AANET_EINVAL;
+  // the resized term's per-image buffer resource (s2_epilogue r_up) has 32-bit sizes too
+  if (terms && terms->up && (long)co_a * terms->up_h * terms->up_w * 4 >= (1L << 31))
+    return AANET_EUNSUPPORTED;
   if (n == 0 || h == 0 || w == 0) return AANET_OK;
   S2Args a;
   a.x = x;

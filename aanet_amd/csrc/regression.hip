@@ -87,19 +87,27 @@ __global__ __launch_bounds__(RB) void disp_regress_bwd_kernel(const float *__res
   if (e >= total) return;
   const long b = e / HW, p = e % HW;
   const float *c = cost + b * D * HW + p;
-  float m = -INFINITY;
-  for (int d = 0; d < D; ++d) m = fmaxf(m, sign * c[(long)d * HW]);
+  float m = sign * c[0];
+  int dm = 0;  // the (first) arg max
+  for (int d = 1; d < D; ++d) {
+    const float s = sign * c[(long)d * HW];
+    if (s > m) m = s, dm = d;
+  }
+  // the mean is taken as an offset from the arg max: mu - dm = sum_d p_d (d - dm).  With a
+  // peaked softmax (p_dm ~ 1) the direct d - mu cancels to nothing at d = dm -- the largest
+  // gradient of the pixel came out 0 or rounding noise of size eps * dm, and the gradients no
+  // longer summed to zero; the offset form keeps every term to relative precision.
   float z = 0.f, acc = 0.f;
   for (int d = 0; d < D; ++d) {
     const float ev = expf(sign * c[(long)d * HW] - m);
     z += ev;
-    acc += ev * (float)d;
+    acc += ev * (float)(d - dm);
   }
-  const float inv = 1.f / z, mu = acc * inv, g = gdisp[e];
+  const float inv = 1.f / z, off = acc * inv, g = gdisp[e];
   float *gc = gcost + b * D * HW + p;
   for (int d = 0; d < D; ++d) {
     const float pr = expf(sign * c[(long)d * HW] - m) * inv;
-    gc[(long)d * HW] = sign * g * pr * ((float)d - mu);
+    gc[(long)d * HW] = sign * g * pr * ((float)(d - dm) - off);
   }
 }
 

@@ -94,6 +94,42 @@ def test_descriptor_size_is_checked_without_a_gpu():
                                        C.byref(t), None) == _lib.EABI
 
 
+def test_corr_volume_bwd_refuses_its_lds_limit_without_a_gpu():
+    """aanet_corr_volume_bwd_f32 stages 4 (D + 8)(64 + 2 (D - 1)) bytes of grad_out in LDS: D = 124
+    is the last size within the CU's 160 KiB (162,096 B), D = 125 (165,312 B) must come back as
+    AANET_EUNSUPPORTED from the host check, before anything is launched (the pointers are dummies
+    that a launch would fault on), and as an AanetError through _lib.call.  Catches a launcher
+    that drops the refusal or moves it behind the launch."""
+    import ctypes as C
+    L = _lib.lib()
+    assert 4 * (124 + 8) * (64 + 2 * 123) <= 160 * 1024 < 4 * (125 + 8) * (64 + 2 * 124)
+    p = C.c_void_p(16)  # never dereferenced: the size check comes first
+    args = (p, p, p, p, p, 1, 4, 1, 64, 125, None)
+    assert L.aanet_corr_volume_bwd_f32(*args) == _lib.EUNSUPPORTED
+    with pytest.raises(_lib.AanetError) as e:
+        _lib.call("aanet_corr_volume_bwd_f32", *args)
+    assert e.value.status == _lib.EUNSUPPORTED
+
+
+def test_conv3x3s2_terms_refuses_an_oversized_up_tensor_without_a_gpu():
+    """aanet_conv3x3s2_terms_f32 reads the resized CSA term through a per-image buffer resource
+    with 32-bit sizes (co_a * up_h * up_w * 4 bytes): an `up` of 2^31 bytes or more per image must
+    be AANET_EUNSUPPORTED like the other three tensors' bounds, on the host (dummy pointers).
+    Catches a launcher whose resource size wraps and lets every `up` load fall out of range."""
+    import ctypes as C
+    L = _lib.lib()
+    p = C.c_void_p(16)
+    # 16 channels x 8192 x 4096 floats = 2^31 bytes, the first size refused
+    big = _lib.S2Terms(None, 0, None, p, 8192, 4096)
+    args = lambda t: (p, p, None, 1, 32, 8, 8, 16, 16, p, 0, None, 0, C.byref(t), None)  # noqa: E731
+    assert L.aanet_conv3x3s2_terms_f32(*args(big)) == _lib.EUNSUPPORTED
+    with pytest.raises(_lib.AanetError) as e:
+        _lib.call("aanet_conv3x3s2_terms_f32", *args(big))
+    assert e.value.status == _lib.EUNSUPPORTED
+    # up_h = 0 stays an invalid argument (checked before the size)
+    assert L.aanet_conv3x3s2_terms_f32(*args(_lib.S2Terms(None, 0, None, p, 0, 4096))) == -1
+
+
 def test_import_leaves_global_torch_flags_alone():
     """importing the package no longer turns TF32 off process-wide; the package's module
     forwards switch it off for their own MIOpen convs and restore it."""

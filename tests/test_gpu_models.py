@@ -44,6 +44,85 @@ def test_disp_warp_backward_vs_oracle(tag):
     assert lhs == pytest.approx(rhs, rel=1e-5, abs=1e-4)
 
 
+# W - 1 is no power of two except at W = 2, so x -> 2 (x / (W-1)) - 1 -> ((. + 1) / 2) (W-1) rounds
+# (the fixtures' W = 17 / 33 make that round trip exact); H = 2 and W = 2 are the smallest sizes
+# the host check admits; 300 x 2 spans two workgroups
+WARP_SHAPES = [(2, 3, 7, 23), (1, 32, 3, 130), (3, 3, 5, 96), (1, 1, 2, 2), (1, 3, 300, 2)]
+_WARP_CASES = {}
+
+
+def _warp_case(shape):
+    """Inputs and references of one warp shape, computed once: disparities uniform in
+    [-0.1 W, 0.6 W) (negative ones included), the first row starting 0, 1, 2.5, W + 3, -2, 0.5 and
+    the last row rounded to integers (sample positions on the pixel grid, where the floor decides);
+    forward, mask and disparity gradient from the oracle; the image gradient from torch's CPU
+    float64 grid_sample autograd on the oracle's float32 sampling positions."""
+    if shape in _WARP_CASES:
+        return _WARP_CASES[shape]
+    B, C, H, W = shape
+    # (seeds at which every shape, the four pixels of 2 x 2 too, has an invalid position)
+    rng = np.random.default_rng(1 + B * 1000 + C * 100 + H + W)
+    img = rng.standard_normal(shape).astype(np.float32)
+    disp = rng.uniform(-0.1 * W, 0.6 * W, (B, 1, H, W)).astype(np.float32)
+    head = np.array([0, 1, 2.5, W + 3, -2, 0.5], np.float32)[:W]
+    disp[0, 0, 0, :len(head)] = head
+    disp[-1, 0, -1] = np.round(disp[-1, 0, -1])
+    go = rng.standard_normal(shape).astype(np.float32)
+    warped, valid = oracle.disp_warp(img, disp)
+    ix, iy = (torch.from_numpy(a.astype(np.float64)) for a in oracle._warp_coords(disp, H, W))
+    grid = torch.stack((2 * ix / (W - 1) - 1, 2 * iy / (H - 1) - 1), -1)
+    img64 = torch.from_numpy(img).double().requires_grad_()
+    w64 = torch.nn.functional.grid_sample(img64, grid, mode="bilinear", padding_mode="border",
+                                          align_corners=True)
+    # the construction is the oracle's warp (its forward to rounding), so its autograd is the
+    # image gradient of that warp
+    assert np.abs(w64.detach().numpy() - warped).max() <= 1e-6
+    (w64 * torch.from_numpy(go).double()).sum().backward()
+    case = dict(img=img, disp=disp, go=go, warped=warped, valid=valid,
+                grad_disp=oracle.disp_warp_bwd(img, disp, go), grad_img=img64.grad.numpy())
+    _WARP_CASES[shape] = case
+    return case
+
+
+@pytest.mark.parametrize("shape", WARP_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_disp_warp_edge_shapes_vs_oracle(shape):
+    """Warped values within 1e-5 and the validity mask identical to the oracle's, with both mask
+    values present.  Catches a sampling position computed without the reference's round trip
+    (x - d used directly: the floor picks the other pixel pair at integer disparities and the mask
+    flips where the corner weights sum to 0.9999), a border clip that lets negative disparities
+    read past the row's end, and a pixel index that assumes W > 2 or one workgroup."""
+    c = _warp_case(shape)
+    warped, valid = nets.disp_warp(torch.from_numpy(c["img"]).to(DEV),
+                                   torch.from_numpy(c["disp"]).to(DEV))
+    assert np.abs(warped.cpu().numpy() - c["warped"]).max() <= 1e-5
+    assert np.array_equal(valid.cpu().numpy(), c["valid"])
+    assert 0.0 < float(c["valid"].mean()) < 1.0, "the case must hold valid and invalid positions"
+
+
+@pytest.mark.parametrize("shape", WARP_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_disp_warp_edge_shapes_backward(shape):
+    """The disparity gradient against the oracle (1e-4 max(1, max|ref|)) and the image gradient
+    element by element against float64 grid_sample autograd, |err| <= 1e-5 (1 + |ref|): each
+    element is a float-atomic sum of at most a few dozen products of size O(1).  Catches a scatter
+    that adds a corner's weight to the neighbouring pixel or row (invisible to the inner-product
+    check when the image is smooth along x), a corner dropped at the clipped border, a batch or
+    channel stride that only holds for B = 1 / C = 3, and a disparity gradient that passes
+    through the border clip."""
+    c = _warp_case(shape)
+    img = torch.from_numpy(c["img"]).to(DEV).requires_grad_()
+    disp = torch.from_numpy(c["disp"]).to(DEV).requires_grad_()
+    warped, _ = nets.disp_warp(img, disp)
+    (warped * torch.from_numpy(c["go"]).to(DEV)).sum().backward()
+    ref_d = c["grad_disp"]
+    assert np.abs(disp.grad.cpu().numpy() - ref_d).max() <= 1e-4 * max(1.0, np.abs(ref_d).max())
+    ref_i = c["grad_img"]
+    err = np.abs(img.grad.cpu().numpy().astype(np.float64) - ref_i)
+    tol = 1e-5 * (1 + np.abs(ref_i))
+    print(f"warp {shape}: image gradient max |err| {err.max():.3g}, max err / bound "
+          f"{(err / tol).max():.3g}, max |ref| {np.abs(ref_i).max():.3g}")
+    assert (err <= tol).all(), (int((err > tol).sum()), float(err.max()))
+
+
 def test_disp_warp_rejects_bad_shapes():
     img = torch.zeros(1, 3, 4, 5, device=DEV)
     with pytest.raises(ValueError):
@@ -51,9 +130,10 @@ def test_disp_warp_rejects_bad_shapes():
 
 
 # ------------------------------------------------------------------ full models -----------
-def build(tag, fuse=True):
+def build(tag, fuse=True, max_disp=None):
     g = golden(tag)
-    m = nets.AANet(int(g["max_disp"]), 1, **json.loads(str(g["config"])))
+    m = nets.AANet(int(g["max_disp"]) if max_disp is None else max_disp, 1,
+                   **json.loads(str(g["config"])))
     fill_synthetic(m, int(g["seed"]), fixture_scales(g))
     m = m.to(DEV).eval()
     for mod in m.modules():
@@ -212,19 +292,41 @@ def test_aanetplus_c3_full_size_properties():
     print("AANet+ 576x960: disparity ranges", [(float(d.min()), float(d.max())) for d in pyr])
 
 
-def test_full_model_training_step():
-    """AANet with intermediate supervision in train mode: the 5-level pyramid, the reference
-    loss weights, backward through every HIP kernel (DCN in the feature extractor and the
-    aggregation, warp in the refinement), finite non-zero gradients everywhere."""
-    g, m, left, right = build("model_aanet_inter")
+# (fixture, max_disp or None for the fixture's, levels in train mode, top-level parameter groups)
+TRAIN_STEPS = [
+    ("model_aanet_inter", None, 5, ("feature_extractor", "fpn", "aggregation", "refinement")),
+    # GCNet-AA at the reference's max_disp = 192: the correlation pyramid runs D = 96 / 48 / 24
+    ("model_gcnet_aa", 192, 2, ("feature_extractor", "fpn", "aggregation", "refinement")),
+    ("model_stereonet_3d", None, 3, ("feature_extractor", "aggregation", "refinement")),  # difference
+    # not here: model_gcnet_3d (the concat volume's backward inside a model).  Its step passes but
+    # takes 11.7 s on the MI355X (GC-Net's 3-D convolutions and their backwards go through MIOpen),
+    # too long for a case of this suite; the concat backward is held at op level
+    # (test_gpu_kernels.py test_shift_volume_backward_vs_oracle)
+]
+
+
+@pytest.mark.parametrize("tag,max_disp,levels,tops", TRAIN_STEPS, ids=[t[0] for t in TRAIN_STEPS])
+def test_full_model_training_step(tag, max_disp, levels, tops):
+    """One training step of a whole model on its fixture's images, backward through every HIP
+    kernel it uses, finite non-zero gradients everywhere.  AANet with intermediate supervision:
+    the 5-level pyramid, the reference loss weights, DCN in the feature extractor and the
+    aggregation, warp in the refinement.  GCNet-AA at max_disp = 192: the correlation pyramid's
+    backward at D = 96 (more than 64 KB of LDS) inside a model.  StereoNet (3-D): the difference
+    volume's backward and the StereoNet refinement's warp.
+    Catches a cost-volume or regression backward that returns no gradient, zeros (a feature
+    extractor left untrained) or a refused launch inside autograd."""
+    g, m, left, right = build(tag, max_disp=max_disp)
     m.train()
     pyr = m(left, right)
-    assert len(pyr) == 5
+    assert len(pyr) == levels
     gt = torch.rand(left.shape[0], *left.shape[2:], device=DEV) * 40 + 1
-    total, per = train.disparity_loss(pyr, gt, gt > 0)
+    # (the reference has no weights for a 2-level pyramid, model.py:109-134: ones)
+    weights = None if levels in train.PYRAMID_WEIGHTS else [1.0] * levels
+    total, per = train.disparity_loss(pyr, gt, gt > 0, weights)
     total.backward()
     assert torch.isfinite(total)
-    groups = {"feature_extractor": 0.0, "fpn": 0.0, "aggregation": 0.0, "refinement": 0.0}
+    groups = {top: 0.0 for top in tops}
+    assert {name.split(".")[0] for name, _ in m.named_parameters()} == set(tops)
     for name, p in m.named_parameters():
         assert p.grad is not None, name
         assert torch.isfinite(p.grad).all(), name
