@@ -60,6 +60,7 @@ _SIGNATURES = {
     "aanet_conv3x3_grouped_nhwc_f32": [_P, _P, _P] + [_I] * 7 + [_P, _P],
     "aanet_mdcn_im2col_f32": [_P, _P, _P, _P] + [_I] * 9 + [_P],
     "aanet_mdcn_sample_index": [_P, _P, _P, _P] + [_I] * 9 + [_P],
+    "aanet_conv_engine_plan": [_P, _P],
 }
 
 # size / query functions (not int-status): name, argtypes, restype
@@ -227,6 +228,23 @@ class S2Terms(_Descriptor):
     _fields_ = [("struct_size", ctypes.c_size_t), ("x2", ctypes.c_void_p), ("c2", ctypes.c_int),
                 ("identity", ctypes.c_void_p), ("up", ctypes.c_void_p), ("up_h", ctypes.c_int),
                 ("up_w", ctypes.c_int)]
+
+
+class ConvPlanQuery(_Descriptor):
+    """aanet_conv_plan_query_t (include/aanet_mi355x.h)."""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("mode", _I), ("n", _I), ("c", _I), ("h", _I),
+                ("w", _I), ("co", _I), ("co2", _I), ("kh", _I), ("kw", _I), ("stride", _I),
+                ("pad", _I), ("dil", _I), ("groups", _I), ("dg", _I), ("layout", _I),
+                ("packed", _I), ("csa", _I), ("num_up", _I), ("up_h", _I * 3), ("up_w", _I * 3),
+                ("post", _I)]
+
+
+class ConvPlan(_Descriptor):
+    """aanet_conv_plan_t (include/aanet_mi355x.h)."""
+    _fields_ = [("struct_size", ctypes.c_size_t), ("status", _I), ("co_t", _I), ("ptt", _I),
+                ("cfg", _I), ("full", _I), ("halo", _I), ("prec", _I), ("layout", _I),
+                ("tail", _I), ("post", _I), ("packed", _I), ("grid_x", _I), ("grid_y", _I),
+                ("last_tile_pixels", _I), ("last_tile_rows", _I), ("last_tile_cols", _I)]
 
 
 ABI_VERSION = 4  # AANET_ABI_VERSION (include/aanet_mi355x.h)

@@ -2447,16 +2447,22 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const T *__restrict__
   }
 }
 
-int check_shapes(const MdcnArgs &a) {
-  if (a.N <= 0 || a.C <= 0 || a.H <= 0 || a.W <= 0 || a.Co <= 0 || a.kh <= 0 || a.kw <= 0 ||
-      a.stride <= 0 || a.pad < 0 || a.dil <= 0 || a.groups <= 0 || a.dg <= 0)
+int check_sizes(int N, int C, int H, int W, int Co, int kh, int kw, int stride, int pad, int dil,
+                int groups, int dg, int Ho, int Wo) {
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || Co <= 0 || kh <= 0 || kw <= 0 || stride <= 0 ||
+      pad < 0 || dil <= 0 || groups <= 0 || dg <= 0)
     return AANET_EINVAL;
-  if (a.C % a.groups || a.Co % a.groups || a.C % a.dg) return AANET_EINVAL;
-  if (a.Ho <= 0 || a.Wo <= 0) return AANET_EINVAL;
+  if (C % groups || Co % groups || C % dg) return AANET_EINVAL;
+  if (Ho <= 0 || Wo <= 0) return AANET_EINVAL;
   // one image's planes are addressed by 32-bit buffer offsets (the epilogues)
-  if ((long)a.C * a.H * a.W * 4 >= (1L << 31) || (long)a.Co * a.Ho * a.Wo * 4 >= (1L << 31))
+  if ((long)C * H * W * 4 >= (1L << 31) || (long)Co * Ho * Wo * 4 >= (1L << 31))
     return AANET_EUNSUPPORTED;
   return AANET_OK;
+}
+
+int check_shapes(const MdcnArgs &a) {
+  return check_sizes(a.N, a.C, a.H, a.W, a.Co, a.kh, a.kw, a.stride, a.pad, a.dil, a.groups, a.dg,
+                     a.Ho, a.Wo);
 }
 
 MdcnArgs make_args(const float *x, const float *offset, long off_bs, const float *mask,
@@ -2509,8 +2515,9 @@ MdcnArgs make_args(const float *x, const float *offset, long off_bs, const float
     a.up[j] = nullptr;
     a.up_h[j] = a.up_w[j] = a.up_r[j] = 1;
   }
-  a.Ho = conv_out_size(h, kh, stride, pad, dil);
-  a.Wo = conv_out_size(w, kw, stride, pad, dil);
+  // stride <= 0 is refused by check_shapes; the output size must not divide by it first
+  a.Ho = stride > 0 ? conv_out_size(h, kh, stride, pad, dil) : 0;
+  a.Wo = stride > 0 ? conv_out_size(w, kw, stride, pad, dil) : 0;
   const long P = (long)a.Ho * a.Wo, K = (long)kh * kw;
   a.off_bs = off_bs >= 0 ? off_bs : (long)dg * 2 * K * P;
   a.mask_bs = mask_bs >= 0 ? mask_bs : (long)dg * K * P;
@@ -2546,37 +2553,38 @@ DcnSmallArgs small_args(const MdcnArgs &a, const float *weight, int packed) {
   return t;
 }
 
+// Every run-time choice below reads the plan (conv_engine_plan), never the arguments.
 template <int MODE, int CO_T, int PTT, int FULL, int CFG>
-void launch_fwd_f(const MdcnArgs &a, int packed, dim3 grid, hipStream_t st) {
+void launch_fwd_f(const MdcnArgs &a, const aanet_conv_plan_t &pl, dim3 grid, hipStream_t st) {
   const dim3 blk(FNT);
   if constexpr (!FULL && MODE == 0 && CFG == 0 && CO_T >= 32) {
     // plain NCHW conv, group width 16 (mod 32): split-bf16 over zero-padded 32-channel chunks
-    if (a.split && packed && !a.tail_w && a.layout == 0) {
+    if (pl.prec) {
       hipLaunchKernelGGL((conv_fwd_kernel<0, CO_T, PTT, 1, 0, 1, 0, 0, 0, 1>), grid, blk, 0, st, a);
       return;
     }
   }
   if constexpr (FULL && CFG == 0 && CO_T >= 32) {  // split-bf16 contraction (PREC 1)
     if constexpr (MODE == 0 && PTT == 128) {
-      if (a.split && packed && a.halo == 4) {  // phase-strided halo tile (dilation > 2)
-        if (a.layout == 3)
+      if (pl.halo == 4) {  // phase-strided halo tile (dilation > 2)
+        if (pl.layout == 3)
           hipLaunchKernelGGL((conv_fwd_kernel<0, CO_T, 128, 1, 0, 1, 1, 3, CFG, 1, 4>), grid, blk, 0, st, a);
         return;
       }
-      if (a.split && packed && a.halo == 1) {  // 3x3 stride-1 halo-tile form (NHWC input), HALO = dil
-        if (a.dil == 1) {
-          if (a.tail_w && a.post && CO_T == 64)
+      if (pl.halo == 1 || pl.halo == 2) {  // 3x3 stride-1 halo-tile form (NHWC input), HALO = dil
+        if (pl.halo == 1) {
+          if (pl.tail && pl.post && CO_T == 64)
             hipLaunchKernelGGL((conv_fwd_kernel<0, CO_T, 128, 1, 1, 1, 1, 1, CFG, 1, 1, 1>), grid, blk, 0, st, a);
-          else if (a.tail_w)
+          else if (pl.tail)
             hipLaunchKernelGGL((conv_fwd_kernel<0, CO_T, 128, 1, 1, 1, 1, 1, CFG, 1, 1>), grid, blk, 0, st, a);
-          else if (a.layout == 3)
+          else if (pl.layout == 3)
             hipLaunchKernelGGL((conv_fwd_kernel<0, CO_T, 128, 1, 0, 1, 1, 3, CFG, 1, 1>), grid, blk, 0, st, a);
           else
             hipLaunchKernelGGL((conv_fwd_kernel<0, CO_T, 128, 1, 0, 1, 1, 1, CFG, 1, 1>), grid, blk, 0, st, a);
         } else {
-          if (a.tail_w)
+          if (pl.tail)
             hipLaunchKernelGGL((conv_fwd_kernel<0, CO_T, 128, 1, 1, 1, 1, 1, CFG, 1, 2>), grid, blk, 0, st, a);
-          else if (a.layout == 3)
+          else if (pl.layout == 3)
             hipLaunchKernelGGL((conv_fwd_kernel<0, CO_T, 128, 1, 0, 1, 1, 3, CFG, 1, 2>), grid, blk, 0, st, a);
           else
             hipLaunchKernelGGL((conv_fwd_kernel<0, CO_T, 128, 1, 0, 1, 1, 1, CFG, 1, 2>), grid, blk, 0, st, a);
@@ -2584,15 +2592,15 @@ void launch_fwd_f(const MdcnArgs &a, int packed, dim3 grid, hipStream_t st) {
         return;
       }
     }
-    if (a.split && packed) {
-      if (a.tail_w) {
-        if (a.layout == 1)
+    if (pl.prec) {
+      if (pl.tail) {
+        if (pl.layout == 1)
           hipLaunchKernelGGL((conv_fwd_kernel<MODE, CO_T, PTT, 1, 1, 1, 1, 1, CFG, 1>), grid, blk, 0, st, a);
         else
           hipLaunchKernelGGL((conv_fwd_kernel<MODE, CO_T, PTT, 1, 1, 1, 1, 0, CFG, 1>), grid, blk, 0, st, a);
         return;
       }
-      switch (a.layout) {
+      switch (pl.layout) {
         case 1: hipLaunchKernelGGL((conv_fwd_kernel<MODE, CO_T, PTT, 1, 0, 1, 1, 1, CFG, 1>), grid, blk, 0, st, a); break;
         case 2: hipLaunchKernelGGL((conv_fwd_kernel<MODE, CO_T, PTT, 1, 0, 1, 1, 2, CFG, 1>), grid, blk, 0, st, a); break;
         case 3: hipLaunchKernelGGL((conv_fwd_kernel<MODE, CO_T, PTT, 1, 0, 1, 1, 3, CFG, 1>), grid, blk, 0, st, a); break;
@@ -2601,13 +2609,13 @@ void launch_fwd_f(const MdcnArgs &a, int packed, dim3 grid, hipStream_t st) {
       return;
     }
   }
-  if (a.tail_w) {
-    if (FULL && a.layout == 1)
+  if (pl.tail) {
+    if (FULL && pl.layout == 1)
       hipLaunchKernelGGL((conv_fwd_kernel<MODE, CO_T, PTT, 1, 1, 1, FULL, FULL ? 1 : 0, CFG>), grid, blk, 0, st, a);
     else
       hipLaunchKernelGGL((conv_fwd_kernel<MODE, CO_T, PTT, 1, 1, 1, FULL, 0, CFG>), grid, blk, 0, st, a);
-  } else if (packed) {
-    switch (FULL ? a.layout : 0) {
+  } else if (pl.packed) {
+    switch (FULL ? pl.layout : 0) {
       case 1: hipLaunchKernelGGL((conv_fwd_kernel<MODE, CO_T, PTT, 1, 0, 1, FULL, FULL ? 1 : 0, CFG>), grid, blk, 0, st, a); break;
       case 2: hipLaunchKernelGGL((conv_fwd_kernel<MODE, CO_T, PTT, 1, 0, 1, FULL, 2, CFG>), grid, blk, 0, st, a); break;
       case 3: hipLaunchKernelGGL((conv_fwd_kernel<MODE, CO_T, PTT, 1, 0, 1, FULL, FULL ? 3 : 2, CFG>), grid, blk, 0, st, a); break;
@@ -2619,30 +2627,120 @@ void launch_fwd_f(const MdcnArgs &a, int packed, dim3 grid, hipStream_t st) {
 }
 
 // Chunk configuration (conv_fwd_kernel CFG) for which every chunk is full, or -1.
-int full_cfg(const MdcnArgs &a, int mode, int co_t) {
-  const int Cg = a.C / a.groups, cpg = a.C / a.dg;
+int full_cfg(int C, int groups, int dg, int mode, int co_t) {
+  const int Cg = C / groups, cpg = C / dg;
   if (Cg % KC == 0 && (!mode || cpg % KC == 0)) return 0;
   if (mode && Cg % KC == 0 && cpg == 16) return 2;
   if (co_t >= 32 && Cg % 16 == 0 && (!mode || cpg % 16 == 0)) return 1;
   return -1;
 }
 
-template <int MODE, int CO_T, int PTT>
-void launch_fwd_t(const MdcnArgs &a, int packed, dim3 grid, hipStream_t st) {
-  const int cfg = full_cfg(a, MODE, CO_T);
-  if (MODE == 0 && CO_T >= 32 && a.split && packed && !a.tail_w && a.layout == 0 && (a.C / a.groups) % 32) {
-    launch_fwd_f<MODE, CO_T, PTT, 0, 0>(a, packed, grid, st);  // zero-padded split chunks
-    return;
+int split_selected(int flags, int packed);
+
+// Every decision of the engine's launch (aanet_conv_engine_plan, include/aanet_mi355x.h): the
+// size checks, the tile (co_t x ptt), the chunk configuration, the halo form, the contraction,
+// the instance's layout and the grid.  Pure host code; launch_fwd launches what it returns.
+// -> the status the launch would return; pl's other members are filled when it is AANET_OK.
+int conv_engine_plan(const aanet_conv_plan_query_t &q, aanet_conv_plan_t &pl) {
+  const int mode = q.mode;
+  if (mode != 0 && mode != 1) return AANET_EINVAL;
+  const int dg = mode ? q.dg : 1;
+  if (q.stride <= 0) return AANET_EINVAL;  // before the output size divides by it
+  const int Ho = conv_out_size(q.h, q.kh, q.stride, q.pad, q.dil);
+  const int Wo = conv_out_size(q.w, q.kw, q.stride, q.pad, q.dil);
+  const int rc = check_sizes(q.n, q.c, q.h, q.w, q.co, q.kh, q.kw, q.stride, q.pad, q.dil, q.groups,
+                             dg, Ho, Wo);
+  if (rc) return rc;
+  if (mode && q.w < 2) return AANET_EUNSUPPORTED;  // pair-gather sampler needs 2 columns
+  const int layout = q.layout & ~(AANET_CONV_EXACT_F32 | AANET_CONV_WEIGHTS_SPLIT |
+                                  (mode ? AANET_CONV_GENERIC_DCN : 0));
+  if (layout < 0 || layout > 3) return AANET_EINVAL;
+  const int packed = q.packed != 0, split = split_selected(q.layout, packed), tail = q.co2 != 0;
+  const long P = (long)Ho * Wo;
+  const int Cog = q.co / q.groups;
+  if (q.csa) {  // CSA epilogue: tail kernels, quad-aligned rows, exact 2x / 4x terms
+    if (!tail || Wo % 4 || q.num_up < 0 || q.num_up > 2) return AANET_EUNSUPPORTED;
+    for (int j = 0; j < q.num_up; ++j) {
+      const int r = q.up_h[j] > 0 ? Ho / q.up_h[j] : 0;
+      if ((r != 2 && r != 4) || q.up_h[j] * r != Ho || q.up_w[j] * r != Wo)
+        return AANET_EUNSUPPORTED;
+    }
   }
-  constexpr bool C1 = CO_T >= 32 && PTT == 128;  // 16-channel chunks: 4 staged values per thread
-  if (cfg == 0)
-    launch_fwd_f<MODE, CO_T, PTT, 1, 0>(a, packed, grid, st);
-  else if (cfg == 1 && C1)
-    launch_fwd_f<MODE, CO_T, PTT, 1, C1 ? 1 : 0>(a, packed, grid, st);
-  else if (cfg == 2 && MODE)
-    launch_fwd_f<MODE, CO_T, PTT, 1, MODE ? 2 : 0>(a, packed, grid, st);
+  int co_t = Cog <= 16 ? 16 : (Cog <= 32 ? 32 : 64);
+  if (tail) {  // the whole conv output column of a pixel must sit in one workgroup
+    if (q.groups != 1 || q.co > 64 || q.co2 <= 0 || q.co2 > 64 || !packed) return AANET_EUNSUPPORTED;
+    co_t = max(q.co, q.co2) <= 16 ? 16 : (max(q.co, q.co2) <= 32 ? 32 : 64);
+  }
+  const int cfg = full_cfg(q.c, q.groups, dg, mode, co_t);
+  if (layout) {  // NHWC paths: packed weights, full chunks (full_cfg), 4-channel quads
+    if (!packed || q.c % 4 || cfg < 0) return AANET_EUNSUPPORTED;
+    if ((layout & 2) && (tail || Cog % 4)) return AANET_EUNSUPPORTED;
+  }
+  const int ncot = host_div_up(Cog, co_t);
+  // 128-pixel tiles when they still give >= 2 workgroups per CU (the scale-1 convs of the C2
+  // pyramid, 832 tiles: stride-2 64->64 exchange conv 93 -> 86 us), else 64
+  int ptt = co_t == 16 || (long)q.n * host_div_up(P, 128) * q.groups * ncot >= 512 ? 128 : 64;
+  if (cfg == 1) ptt = 128;  // 16-channel chunks are staged 4 per thread
+  const bool s1_3x3 = mode == 0 && split && q.kh == 3 && q.kw == 3 && q.stride == 1 &&
+                      q.pad == q.dil && co_t >= 32 && cfg == 0;
+  // 3x3 stride-1 halo tile on NHWC input, HALO = dil (1 or 2)
+  int halo = s1_3x3 && (layout & 1) && q.dil <= 2 ? q.dil : 0;
+  // dilations > 2 (the refinement's dilated blocks): the phase-strided halo tile (HALO 4),
+  // NHWC in and out, no tail
+  if (!halo && s1_3x3 && layout == 3 && q.dil > 2 && !tail && !q.csa && !q.post) halo = 4;
+  if (halo) ptt = 128;
+  // post stage (aanet_post_stage_t): the HALO 1 tail with the CSA epilogue, 64 -> 64 channels,
+  // NHWC output only; anything else is left to the caller before any launch
+  if (q.post && (mode != 0 || !q.csa || halo != 1 || co_t != 64 || q.co2 != 64 || q.post != 1 || !split))
+    return AANET_EUNSUPPORTED;
+  // the instance: guarded or full chunks (a split pack of group width 16 mod 32 runs the plain
+  // NCHW conv over zero-padded 32-channel chunks, FULL 0 with PREC 1)
+  const bool padded = mode == 0 && co_t >= 32 && split && !tail && layout == 0 && (q.c / q.groups) % 32;
+  pl.full = !padded && (cfg == 0 || (cfg == 1 && co_t >= 32 && ptt == 128) || (cfg == 2 && mode));
+  pl.cfg = pl.full ? cfg : 0;
+  pl.prec = padded || (pl.full && pl.cfg == 0 && co_t >= 32 && split);
+  pl.halo = halo;
+  pl.tail = tail;
+  pl.post = halo == 1 && tail && q.post && co_t == 64;
+  pl.packed = packed;
+  if (halo)
+    pl.layout = tail ? 1 : (layout == 3 ? 3 : 1);
+  else if (tail)
+    pl.layout = pl.full && layout == 1 ? 1 : 0;
   else
-    launch_fwd_f<MODE, CO_T, PTT, 0, 0>(a, packed, grid, st);
+    pl.layout = packed && pl.full ? layout : 0;
+  pl.co_t = co_t;
+  pl.ptt = ptt;
+  const int hd = halo == 4 ? q.dil : 1;  // phase stride (HALO 4)
+  const int wh = host_div_up(Wo, hd), hh = host_div_up(Ho, hd);
+  pl.grid_x = (int)(unsigned)(halo ? (long)q.n * hd * hd * host_div_up(wh, 16) * host_div_up(hh, 8)
+                                   : q.n * host_div_up(P, ptt));
+  pl.grid_y = q.groups * ncot;
+  if (halo) {
+    pl.last_tile_cols = wh % 16;
+    pl.last_tile_rows = hh % 8;
+    pl.last_tile_pixels = pl.last_tile_cols || pl.last_tile_rows
+                              ? (pl.last_tile_cols ? pl.last_tile_cols : 16) *
+                                    (pl.last_tile_rows ? pl.last_tile_rows : 8)
+                              : 0;
+  } else {
+    pl.last_tile_cols = pl.last_tile_rows = 0;
+    pl.last_tile_pixels = (int)(P % ptt);
+  }
+  return AANET_OK;
+}
+
+template <int MODE, int CO_T, int PTT>
+void launch_fwd_t(const MdcnArgs &a, const aanet_conv_plan_t &pl, dim3 grid, hipStream_t st) {
+  constexpr bool C1 = CO_T >= 32 && PTT == 128;  // 16-channel chunks: 4 staged values per thread
+  if (!pl.full)
+    launch_fwd_f<MODE, CO_T, PTT, 0, 0>(a, pl, grid, st);
+  else if (pl.cfg == 1 && C1)
+    launch_fwd_f<MODE, CO_T, PTT, 1, C1 ? 1 : 0>(a, pl, grid, st);
+  else if (pl.cfg == 2 && MODE)
+    launch_fwd_f<MODE, CO_T, PTT, 1, MODE ? 2 : 0>(a, pl, grid, st);
+  else
+    launch_fwd_f<MODE, CO_T, PTT, 1, 0>(a, pl, grid, st);
 }
 
 template <int MODE>
@@ -2652,63 +2750,50 @@ int launch_fwd(const MdcnArgs &a_in, int packed, hipStream_t st) {
   if (rc) return rc;
   if (!a.x || !a.weight || !a.out) return AANET_EINVAL;
   if (MODE && (!a.offset || !a.mask)) return AANET_EINVAL;
-  if (MODE && a.W < 2) return AANET_EUNSUPPORTED;  // pair-gather sampler needs 2 columns
   if (a.post_scale && !a.post_shift) return AANET_EINVAL;
-  const long P = (long)a.Ho * a.Wo;
-  const int Cog = a.Co / a.groups;
-  if (a.layout < 0 || a.layout > 3) return AANET_EINVAL;
-  if (a.csa_out) {  // CSA epilogue: tail kernels, quad-aligned rows, exact 2x / 4x terms
-    if (!a.tail_w || a.Wo % 4 || a.num_up < 0 || a.num_up > 2) return AANET_EUNSUPPORTED;
-    for (int j = 0; j < a.num_up; ++j) {
-      const int r = a.up_r[j];
-      if (!a.up[j] || (r != 2 && r != 4) || a.up_h[j] * r != a.Ho || a.up_w[j] * r != a.Wo)
-        return AANET_EUNSUPPORTED;
-    }
+  // everything else is decided by conv_engine_plan, from the sizes alone
+  aanet_conv_plan_query_t q{};
+  q.struct_size = sizeof(q);
+  q.mode = MODE;
+  q.n = a.N;
+  q.c = a.C;
+  q.h = a.H;
+  q.w = a.W;
+  q.co = a.Co;
+  q.co2 = a.tail_w ? (a.Co2 > 0 ? a.Co2 : -1) : 0;
+  q.kh = a.kh;
+  q.kw = a.kw;
+  q.stride = a.stride;
+  q.pad = a.pad;
+  q.dil = a.dil;
+  q.groups = a.groups;
+  q.dg = a.dg;
+  q.layout = a.layout | (a.split ? AANET_CONV_WEIGHTS_SPLIT : 0);
+  q.packed = packed;
+  q.csa = a.csa_out != nullptr;
+  q.num_up = a.num_up;
+  for (int j = 0; j < 3; ++j) {
+    q.up_h[j] = a.up_h[j];
+    q.up_w[j] = a.up_w[j];
   }
-  int co_t = Cog <= 16 ? 16 : (Cog <= 32 ? 32 : 64);
-  if (a.tail_w) {  // the whole conv output column of a pixel must sit in one workgroup
-    if (a.groups != 1 || a.Co > 64 || a.Co2 <= 0 || a.Co2 > 64 || !packed) return AANET_EUNSUPPORTED;
-    co_t = max(a.Co, a.Co2) <= 16 ? 16 : (max(a.Co, a.Co2) <= 32 ? 32 : 64);
-  }
-  if (a.layout) {  // NHWC paths: packed weights, full chunks (full_cfg), 4-channel quads
-    if (!packed || a.C % 4 || full_cfg(a, MODE, co_t) < 0) return AANET_EUNSUPPORTED;
-    if ((a.layout & 2) && (a.tail_w || Cog % 4)) return AANET_EUNSUPPORTED;
-  }
-  const int ncot = host_div_up(Cog, co_t);
-  // 128-pixel tiles when they still give >= 2 workgroups per CU (the scale-1 convs of the C2
-  // pyramid, 832 tiles: stride-2 64->64 exchange conv 93 -> 86 us), else 64
-  int ptt = co_t == 16 || (long)a.N * host_div_up(P, 128) * a.groups * ncot >= 512 ? 128 : 64;
-  if (full_cfg(a, MODE, co_t) == 1) ptt = 128;  // 16-channel chunks are staged 4 per thread
-  a.halo = MODE == 0 && a.split && packed && (a.layout & 1) && a.kh == 3 && a.kw == 3 &&
-           a.stride == 1 && a.pad == a.dil && a.dil <= 2 && co_t >= 32 && full_cfg(a, 0, co_t) == 0;
-  // dilations > 2 (the refinement's dilated blocks): the phase-strided halo tile (HALO 4),
-  // NHWC in and out, no tail
-  if (!a.halo && MODE == 0 && a.split && packed && a.layout == 3 && a.kh == 3 && a.kw == 3 &&
-      a.stride == 1 && a.pad == a.dil && a.dil > 2 && co_t >= 32 && !a.tail_w && !a.csa_out &&
-      !a.post && full_cfg(a, 0, co_t) == 0)
-    a.halo = 4;
-  if (a.halo) ptt = 128;
-  // post stage (aanet_post_stage_t): the HALO 1 tail with the CSA epilogue, 64 -> 64 channels,
-  // NHWC output only; anything else is left to the caller before any launch
-  if (a.post && (MODE != 0 || !a.csa_out || !a.halo || a.dil != 1 || co_t != 64 || a.Co2 != 64 ||
-                 a.post->disp || !a.post->out_nhwc || a.post->skip_outputs || !a.split || !packed))
-    return AANET_EUNSUPPORTED;
-  const int hd = a.halo == 4 ? a.dil : 1;  // phase stride (HALO 4)
-  dim3 grid((unsigned)(a.halo ? (long)a.N * hd * hd * host_div_up(host_div_up(a.Wo, hd), 16) *
-                                    host_div_up(host_div_up(a.Ho, hd), 8)
-                              : a.N * host_div_up(P, ptt)),
-            (unsigned)(a.groups * ncot));
-  if (ptt == 128) {
-    switch (co_t) {
-      case 16: launch_fwd_t<MODE, 16, 128>(a, packed, grid, st); break;
-      case 32: launch_fwd_t<MODE, 32, 128>(a, packed, grid, st); break;
-      default: launch_fwd_t<MODE, 64, 128>(a, packed, grid, st); break;
+  q.post = a.post ? (a.post->disp || !a.post->out_nhwc || a.post->skip_outputs ? 2 : 1) : 0;
+  aanet_conv_plan_t pl{};
+  pl.struct_size = sizeof(pl);
+  pl.status = conv_engine_plan(q, pl);
+  if (pl.status) return pl.status;
+  a.halo = pl.halo == 4 ? 4 : (pl.halo ? 1 : 0);
+  const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y);
+  if (pl.ptt == 128) {
+    switch (pl.co_t) {
+      case 16: launch_fwd_t<MODE, 16, 128>(a, pl, grid, st); break;
+      case 32: launch_fwd_t<MODE, 32, 128>(a, pl, grid, st); break;
+      default: launch_fwd_t<MODE, 64, 128>(a, pl, grid, st); break;
     }
   } else {
-    switch (co_t) {
+    switch (pl.co_t) {
       case 16: break;  // unreachable: 16-channel tiles always take 128-pixel tiles
-      case 32: launch_fwd_t<MODE, 32, 64>(a, packed, grid, st); break;
-      default: launch_fwd_t<MODE, 64, 64>(a, packed, grid, st); break;
+      case 32: launch_fwd_t<MODE, 32, 64>(a, pl, grid, st); break;
+      default: launch_fwd_t<MODE, 64, 64>(a, pl, grid, st); break;
     }
   }
   return aanet_launch_status();
@@ -2819,8 +2904,12 @@ __global__ void pack_weight_kernel(const float *__restrict__ w, float *__restric
 // PREC 1 needs weight buffers from aanet_conv_weight_pack_split_f32 (AANET_CONV_WEIGHTS_SPLIT)
 // and the split arithmetic selected (AANET_CONV_EXACT_F32 clear); a tail kernel's pointwise
 // weights then carry their fragments too.
+int split_selected(int flags, int packed) {
+  return packed && (flags & AANET_CONV_WEIGHTS_SPLIT) && !(flags & AANET_CONV_EXACT_F32);
+}
+
 void set_split(MdcnArgs &a, int flags, int packed) {
-  a.split = packed && (flags & AANET_CONV_WEIGHTS_SPLIT) && !(flags & AANET_CONV_EXACT_F32);
+  a.split = split_selected(flags, packed);
   if (!a.split) return;
   const int cg = a.C / a.groups, kk = a.kh * a.kw;
   a.wsplit = reinterpret_cast<const bf16x8_t *>(reinterpret_cast<const char *>(a.weight) +
@@ -3154,6 +3243,16 @@ extern "C" int aanet_mdcn_fwd_fused_f32(const float *x, const float *offset,
     if (rc != AANET_EUNSUPPORTED) return rc;
   }
   return launch_fwd<1>(a, weight_packed, as_hip(stream));
+}
+
+extern "C" int aanet_conv_engine_plan(const aanet_conv_plan_query_t *q, aanet_conv_plan_t *plan) {
+  if (!q || !plan) return AANET_EINVAL;
+  if (q->struct_size != sizeof(*q) || plan->struct_size != sizeof(*plan)) return AANET_EABI;
+  aanet_conv_plan_t pl{};
+  pl.struct_size = sizeof(pl);
+  pl.status = conv_engine_plan(*q, pl);
+  *plan = pl;
+  return AANET_OK;
 }
 
 extern "C" int aanet_mdcn_window_fwd_supported(int c, int co, int kh, int kw, int stride, int pad,

@@ -3,6 +3,7 @@
 Each op allocates its outputs with torch (caching allocator, device memory) and launches on
 torch's current HIP stream through ``_lib.call`` -- capturable into a HIP graph.
 """
+import collections
 import ctypes
 
 import torch
@@ -218,6 +219,41 @@ def window_fwd_ok(C, Co, kh, kw, stride, padding, dilation, groups, deformable_g
                                                            groups, deformable_groups, W))
 
 
+EnginePlan = collections.namedtuple(
+    "EnginePlan", "status co_t ptt cfg full halo prec layout tail post packed grid_x grid_y "
+                  "last_tile_pixels last_tile_rows last_tile_cols")
+
+
+def conv_engine_plan(mode, N, C, H, W, Co, kernel, stride=1, padding=0, dilation=1, groups=1,
+                     deformable_groups=1, co2=0, layout=0, packed=True, csa=None, post=0):
+    """Which conv_fwd_kernel instance the implicit-GEMM engine runs for a call, and on what grid
+    (aanet_conv_engine_plan; host only, no GPU needed) -> EnginePlan.
+
+    mode: 0 / "conv" plain, 1 / "dcn" deformable.  kernel: k or (kh, kw).  co2: the fused
+    pointwise tail's output channels (0: no tail).  layout: the C entry points' word,
+    _lib.LAYOUT_* | _lib.CONV_* (conv_flags(...) of the packed weights).  packed: the kernel reads
+    pack_weight / pack_weight_split weights.  csa: None, or the (h, w) of each CSA up term.
+    post: 0 none, 1 the NHWC post stage, 2 any other.  `status` is what the launch would return
+    (0 ok, _lib.EUNSUPPORTED, -1 invalid); the other fields describe the instance when it is 0.
+    Shapes that an entry point diverts to a specialised kernel (direct, pointwise, window DCN,
+    16-channel DCN) are planned as the engine would run them."""
+    kh, kw = (kernel, kernel) if isinstance(kernel, int) else kernel
+    q = _lib.ConvPlanQuery()
+    q.mode = {"conv": 0, "dcn": 1}.get(mode, mode)
+    q.n, q.c, q.h, q.w, q.co, q.co2 = N, C, H, W, Co, co2
+    q.kh, q.kw, q.stride, q.pad, q.dil = kh, kw, stride, padding, dilation
+    q.groups, q.dg, q.layout, q.packed, q.post = groups, deformable_groups, layout, int(bool(packed)), post
+    if csa is not None:
+        if len(csa) > 3:
+            raise ValueError("at most 3 upsampled CSA terms")
+        q.csa, q.num_up = 1, len(csa)
+        for j, (uh, uw) in enumerate(csa):
+            q.up_h[j], q.up_w[j] = uh, uw
+    pl = _lib.ConvPlan()
+    call("aanet_conv_engine_plan", _lib.ctypes.byref(q), _lib.ctypes.byref(pl))
+    return EnginePlan(*(getattr(pl, f) for f in EnginePlan._fields))
+
+
 def _split_weight(weight):
     """pack_weight_split(weight), kept on the weight tensor itself with the (storage, version,
     shape) it was packed from: an optimizer step bumps the version, so training re-packs once per
@@ -283,7 +319,7 @@ def mdcn_forward(x, offset, mask, weight, bias=None, stride=1, padding=0, dilati
 
 def mdcn_forward_fused(x, offset_mask, weight, bias=None, post_scale=None, post_shift=None, act=None,
                        stride=1, padding=0, dilation=1, deformable_groups=1, mask_scale=2.0,
-                       packed_weight=None, groups=1):
+                       packed_weight=None, groups=1, out=None):
     """Eval fast path of DeformConv2d (nets/deform.py:78-97) + BN + activation.
 
     offset_mask is the raw offset_conv output [N, dg*3*K, Ho, Wo]: channels [0, 2*dg*K) are
@@ -301,7 +337,7 @@ def mdcn_forward_fused(x, offset_mask, weight, bias=None, post_scale=None, post_
     Ho, Wo = _out_size(H, kh, stride, padding, dilation), _out_size(W, kw, stride, padding, dilation)
     if offset_mask.shape != (N, deformable_groups * 3 * K, Ho, Wo):
         raise ValueError(f"offset_mask shape {tuple(offset_mask.shape)} unexpected")
-    out = torch.empty((N, Co, Ho, Wo), device=x.device, dtype=x.dtype)
+    out = _own_out(out, (N, Co, Ho, Wo), x)
     bs = offset_mask.stride(0)
     mask_ptr = offset_mask.data_ptr() + 4 * deformable_groups * 2 * K * Ho * Wo
     wsrc = packed_weight if packed_weight is not None else weight
@@ -329,7 +365,8 @@ def pack_weight_split(weight, groups=1):
     """Weight buffer of the split-bf16 contraction (aanet_conv_weight_pack_split_f32): the
     pack_weight layout, followed in the same allocation by the bf16 piece fragments.  Returned as
     the [kh][kw][co][cg] float view of its head (so it is also a valid pack_weight result) and
-    tagged ``_aanet_split``; None when the shape has no split form (cg % 32 != 0)."""
+    tagged ``_aanet_split``; None when the shape has no split form (cg neither a multiple of 32
+    nor 48, 80, ...: 16 mod 32 from 48 up, packed with a zero-padded last chunk)."""
     require_gpu(weight, names=("weight",))
     Co, Cg, kh, kw = weight.shape
     nbytes = _lib.lib().aanet_conv_weight_pack_split_bytes(Co, Cg, kh, kw, groups)
@@ -344,14 +381,28 @@ def pack_weight_split(weight, groups=1):
     return wp
 
 
+def _own_out(out, shape, like, nhwc=False):
+    """The op's result tensor: a fresh one, or the caller's `out` (shape, dtype, device and
+    memory format checked -- the kernel writes through its raw pointer)."""
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=like.dtype,
+                           memory_format=torch.channels_last if nhwc else torch.contiguous_format)
+    ok = _lib.is_nhwc(out) or (shape[1] == 1 and out.is_contiguous()) if nhwc else out.is_contiguous()
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or out.device != like.device or not ok:
+        raise ValueError(f"out must be a {'channels_last' if nhwc else 'contiguous'} {like.dtype} "
+                         f"tensor of shape {tuple(shape)} on {like.device}")
+    return out
+
+
 def conv2d_fused(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, act=None,
                  residual=None, post_scale=None, post_shift=None, packed_weight=None,
-                 out_nhwc=False):
+                 out_nhwc=False, out=None):
     """Plain conv on the HIP implicit-GEMM engine: act(post_scale*(conv+bias)+post_shift+residual).
     weight gives the shape ([co][cg][kh][kw]); packed_weight (pack_weight(weight)) if given is
     what the kernel reads, and then `weight` may be just that shape (a tuple).  x may be
     channels_last (NHWC staging); out_nhwc=True returns a channels_last tensor (residual then
-    channels_last too).  NHWC needs packed_weight and 32-channel groups (AANET_LAYOUT_*)."""
+    channels_last too).  NHWC needs packed_weight and 32-channel groups (AANET_LAYOUT_*).
+    out: a caller-owned result tensor of the output's shape and memory format."""
     if not torch.is_tensor(weight):
         if packed_weight is None:
             raise ValueError("a weight shape alone needs packed_weight")
@@ -370,8 +421,7 @@ def conv2d_fused(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1
               | _lib.conv_flags(packed_weight))
     if residual is not None and out_nhwc and not (_lib.is_nhwc(residual) or Co == 1):
         raise ValueError("residual must be channels_last when out_nhwc=True")
-    out = torch.empty((N, Co, Ho, Wo), device=x.device, dtype=x.dtype,
-                      memory_format=torch.channels_last if out_nhwc else torch.contiguous_format)
+    out = _own_out(out, (N, Co, Ho, Wo), x, out_nhwc)
     wsrc = packed_weight if packed_weight is not None else weight
     call("aanet_conv2d_fused_f32", ptr(x), ptr(wsrc), ptr(bias), ptr(post_scale), ptr(post_shift),
          ptr(residual), ACT[act], int(packed_weight is not None), ptr(out), N, C, H, W, Co, kh, kw,
@@ -444,7 +494,7 @@ def _csa_epilogue(out, csa_up, csa_act):
 
 def conv2d_pw(x, weight, packed_weight, bias, post_scale, post_shift, act, pw_packed, pw_bias,
               residual=None, pw_act=None, stride=1, padding=0, dilation=1, csa_up=None,
-              csa_act="leaky", post=None):
+              csa_act="leaky", post=None, out=None):
     """Plain conv + fused pointwise tail (bottleneck conv2 -> conv3, aanet_conv2d_pw_f32).
     x may be channels_last (NHWC staging); the output is NCHW.  csa_up (list of coarser
     exchange terms): also return the CSA sum act(out + up(csa_up...)) -> (out, csa_out).
@@ -456,7 +506,7 @@ def conv2d_pw(x, weight, packed_weight, bias, post_scale, post_shift, act, pw_pa
     Co, _, kh, kw = weight.shape
     Co2 = pw_packed.shape[-2]
     Ho, Wo = _out_size(H, kh, stride, padding, dilation), _out_size(W, kw, stride, padding, dilation)
-    out = torch.empty((N, Co2, Ho, Wo), device=x.device, dtype=x.dtype)
+    out = _own_out(out, (N, Co2, Ho, Wo), x)
     desc, csa_out = _csa_epilogue(out, csa_up, csa_act)
     ps, pres = _post_stage(out, post if desc is not None else None)
     ran = _call_tail("aanet_conv2d_pw_f32",
@@ -474,7 +524,7 @@ def conv2d_pw(x, weight, packed_weight, bias, post_scale, post_shift, act, pw_pa
 def mdcn_pw(x, offset_mask, weight, packed_weight, bias, post_scale, post_shift, act, pw_packed,
             pw_bias, residual=None, pw_act=None, stride=1, padding=0, dilation=1,
             deformable_groups=1, mask_scale=2.0, csa_up=None, csa_act="leaky", generic_dcn=False,
-            post=None):
+            post=None, out=None):
     """DCN (offset/mask read in place from offset_conv's output) + fused pointwise tail.
     x may be channels_last (NHWC corner loads); the output is NCHW.  csa_up, post: as conv2d_pw.
     generic_dcn: keep the generic engine where the LDS-window tail would run (A/B, tests)."""
@@ -487,7 +537,7 @@ def mdcn_pw(x, offset_mask, weight, packed_weight, bias, post_scale, post_shift,
     Ho, Wo = _out_size(H, kh, stride, padding, dilation), _out_size(W, kw, stride, padding, dilation)
     if offset_mask.shape != (N, deformable_groups * 3 * K, Ho, Wo):
         raise ValueError(f"offset_mask shape {tuple(offset_mask.shape)} unexpected")
-    out = torch.empty((N, Co2, Ho, Wo), device=x.device, dtype=x.dtype)
+    out = _own_out(out, (N, Co2, Ho, Wo), x)
     desc, csa_out = _csa_epilogue(out, csa_up, csa_act)
     ps, pres = _post_stage(out, post if desc is not None else None)
     bs = offset_mask.stride(0)

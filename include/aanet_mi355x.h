@@ -23,7 +23,9 @@ typedef struct ihipStream_t *aanet_stream_t; /* identical to hipStream_t */
 
 /* ABI version (aanet_version()).  4: every descriptor struct starts with `struct_size`
  * (round 4; version 1 had none, and aanet_csa_epilogue_t grew a `post` member in round 3 without
- * a way for the library to tell the two layouts apart). */
+ * a way for the library to tell the two layouts apart).  The version counts descriptor layouts
+ * and signatures of existing entry points: an added entry point with descriptors of its own
+ * (aanet_conv_engine_plan) leaves it alone. */
 #define AANET_ABI_VERSION 4
 
 enum {
@@ -164,6 +166,65 @@ int aanet_mdcn_fwd_fused_f32(const float *x, const float *offset, long offset_ba
  * 32, w % 4 == 0 -- the aggregation's deformable convs (nets/deform.py:216-226). */
 int aanet_mdcn_window_fwd_supported(int c, int co, int kh, int kw, int stride, int pad, int dil,
                                     int groups, int dg, int w);
+
+/* Host-only query of the implicit-GEMM conv engine (conv_fwd_kernel in mdcn.hip, behind
+ * aanet_conv2d_fused_f32, aanet_conv2d_pw_f32, aanet_mdcn_fwd_f32, aanet_mdcn_fwd_fused_f32,
+ * aanet_mdcn_pw_f32 and the deconv phase convs): which kernel instance a call would run and on
+ * what grid.  The engine's launcher takes every one of these decisions from this function, so the
+ * answer cannot drift from what is launched.  Touches no device, launches nothing.
+ *
+ * Scope: the engine itself.  The entry points divert some shapes to specialised kernels before
+ * the engine is asked -- the direct few-channel conv (small_conv.hip: 3 -> <= 32 channels 7x7 / 3
+ * and 3x3, 6 / 1 -> <= 16 and 32 -> 1 3x3 stride 1, dilation 1, one group), the streaming 1x1
+ * (pointwise.hip: split weights, 1x1 stride 1 pad 0, one group, c 32 or 64, co <= 64 or a
+ * multiple of 64 up to 512), the LDS-window DCN (aanet_mdcn_window_fwd_supported, and the tail
+ * form of aanet_mdcn_pw_f32 on NHWC input) and the 16-channel direct DCN (dcn_small.hip).  For
+ * such a shape the plan describes what the engine would run if asked (what
+ * AANET_CONV_GENERIC_DCN forces for the DCNs).  Null-pointer checks are the entry points' too.
+ *
+ * Query: mode 0 plain conv, 1 modulated deformable conv (dg is read for mode 1 only).  co2: output channels of the fused
+ * pointwise tail (aanet_*_pw_f32), 0 = no tail.  layout: the entry points' `layout` word
+ * (AANET_LAYOUT_* | AANET_CONV_*).  packed: the entry points' weight_packed (1 for the tail entry
+ * points).  csa != 0: a CSA epilogue with num_up terms of up_h[j] x up_w[j].  post: 0 none,
+ * 1 a post stage with out_nhwc set, disp NULL and skip_outputs 0 (the form the engine takes),
+ * 2 any other post stage.
+ *
+ * Plan: status is what the launch would return for these sizes (AANET_OK, AANET_EINVAL,
+ * AANET_EUNSUPPORTED); the other members are valid when it is AANET_OK and name the
+ * conv_fwd_kernel instance: co_t output channels (16 / 32 / 64) by ptt pixels (64 / 128) per
+ * workgroup; full 1: every K chunk is full, in chunk configuration cfg (0: 32 channels, 1: 16
+ * channels, 2: 32 channels over two 16-channel deformable groups); 0: guarded chunks; prec 1:
+ * split-bf16 contraction, 0: exact f32 MFMA; halo 0: im2col tiles of ptt consecutive pixels,
+ * 1 / 2: the 16 x 8 halo tile of a 3x3 stride-1 conv of dilation 1 / 2, 4: the phase-strided
+ * halo tile (dilation > 2); layout: the instance's AANET_LAYOUT_* bits; tail / post: the fused
+ * pointwise tail / post stage; packed: reads packed weights.  grid_x, grid_y: the launch grid
+ * (grid_y = groups * ceil(co / groups / co_t)).  last_tile_pixels: valid pixels of an image's
+ * last tile when it is ragged, P % ptt (halo 0; 0: the tiles fit); halo forms report
+ * last_tile_cols = wo' % 16 and last_tile_rows = ho' % 8 instead (wo', ho': the output size, of
+ * phase 0 for halo 4; 0: fits), and last_tile_pixels is the valid pixel count of the bottom-right
+ * tile when either is ragged, else 0.
+ * Returns AANET_EABI for a struct_size mismatch, AANET_EINVAL for a null argument, else
+ * AANET_OK with the verdict in plan->status. */
+typedef struct {
+  size_t struct_size; /* sizeof(aanet_conv_plan_query_t); AANET_EABI otherwise */
+  int mode;
+  int n, c, h, w, co, co2;
+  int kh, kw, stride, pad, dil, groups, dg;
+  int layout;
+  int packed;
+  int csa, num_up, up_h[3], up_w[3];
+  int post;
+} aanet_conv_plan_query_t;
+
+typedef struct {
+  size_t struct_size; /* sizeof(aanet_conv_plan_t); AANET_EABI otherwise */
+  int status;
+  int co_t, ptt, cfg, full, halo, prec, layout, tail, post, packed;
+  int grid_x, grid_y;
+  int last_tile_pixels, last_tile_rows, last_tile_cols;
+} aanet_conv_plan_t;
+
+int aanet_conv_engine_plan(const aanet_conv_plan_query_t *q, aanet_conv_plan_t *plan);
 
 /* Plain convolution on the same implicit-GEMM engine, for the eval fast path of every other
  * conv in the ISA/CSA blocks (nets/deform.py:6-14 conv1x1/conv3x3, nets/deform.py:70-72

@@ -329,3 +329,153 @@ def test_deconv2x_phase_weight_is_the_transposed_conv(ci, co, h, w):
         for b in (0, 1):
             out[:, :, a::2, b::2] = ph[:, 2 * a + b::4, a:a + h, b:b + w]
     assert torch.allclose(out, ref, rtol=0, atol=1e-12)
+
+
+# ------------------------------------------------------- conv engine plan (aanet_conv_engine_plan)
+SPLIT = _lib.CONV_WEIGHTS_SPLIT
+
+
+def test_engine_plan_tile_width_threshold_without_a_gpu():
+    """The engine takes 128-pixel tiles when N * ceil(P / 128) * groups * ncot >= 512, else 64
+    (64 -> 64 3x3 s1 p1, NCHW input, split weights: no halo form): N = 4 at 113 x 145 is 516
+    workgroups with one valid pixel in the last tile, N = 3 (387) stays on 64-pixel tiles, and
+    N = 8 at 65 x 125 sits exactly on 512 with 61 valid pixels in the last."""
+    plan = lambda n, h, w: ops.conv_engine_plan("conv", n, 64, h, w, 64, 3, 1, 1, layout=SPLIT)  # noqa: E731
+    a = plan(4, 113, 145)
+    assert (a.status, a.ptt, a.co_t, a.halo, a.prec, a.full, a.cfg) == (0, 128, 64, 0, 1, 1, 0)
+    assert (a.last_tile_pixels, a.grid_x, a.grid_y) == (1, 4 * 129, 1)
+    b = plan(3, 113, 145)
+    assert (b.status, b.ptt, b.last_tile_pixels, b.grid_x) == (0, 64, 113 * 145 % 64, 3 * 257)
+    c = plan(8, 65, 125)
+    assert (c.status, c.ptt, c.last_tile_pixels, c.grid_x * c.grid_y) == (0, 128, 61, 512)
+    # one workgroup fewer: 7 images are 448 workgroups of 128 pixels
+    assert plan(7, 65, 125).ptt == 64
+    # groups and output-channel tiles count towards the threshold: Co = 128 halves N
+    d = ops.conv_engine_plan("conv", 2, 64, 113, 145, 128, 3, 1, 1, layout=SPLIT)
+    assert (d.ptt, d.grid_x, d.grid_y) == (128, 2 * 129, 2)
+    assert ops.conv_engine_plan("conv", 1, 64, 113, 145, 128, 3, 1, 1, layout=SPLIT).ptt == 64
+
+
+def test_engine_plan_forms_that_always_take_128_pixel_tiles():
+    """co_t = 16, 16-channel chunks (cfg 1) and every halo form run 128-pixel tiles at any size."""
+    p = ops.conv_engine_plan("conv", 1, 5, 7, 9, 3, 3, 1, 1, packed=False)
+    assert (p.status, p.co_t, p.ptt, p.full, p.prec, p.packed) == (0, 16, 128, 0, 0, 0)
+    p = ops.conv_engine_plan("conv", 1, 32, 9, 26, 54, 3, 1, 2, 2, groups=2, layout=1)
+    assert (p.status, p.co_t, p.ptt, p.full, p.cfg, p.prec, p.layout) == (0, 32, 128, 1, 1, 0, 1)
+    for dil, layout, halo in ((1, 1, 1), (2, 1, 2), (1, 3, 1), (4, 3, 4), (8, 3, 4)):
+        p = ops.conv_engine_plan("conv", 1, 64, 9, 26, 64, 3, 1, dil, dil, layout=layout | SPLIT)
+        assert (p.status, p.halo, p.ptt, p.prec, p.layout) == (0, halo, 128, 1, layout), (dil, p)
+    # 9 x 26 on 16 x 8 halo tiles: one ragged row, ten ragged columns
+    p = ops.conv_engine_plan("conv", 1, 64, 9, 26, 64, 3, 1, 1, layout=1 | SPLIT)
+    assert (p.last_tile_rows, p.last_tile_cols, p.last_tile_pixels, p.grid_x) == (1, 10, 10, 4)
+    # the halo forms need the split contraction, NHWC input and stride 1
+    assert ops.conv_engine_plan("conv", 1, 64, 9, 26, 64, 3, 1, 1, layout=1).halo == 0
+    assert ops.conv_engine_plan("conv", 1, 64, 9, 26, 64, 3, 1, 1, layout=SPLIT).halo == 0
+    assert ops.conv_engine_plan("conv", 1, 64, 9, 26, 64, 3, 2, 1, layout=1 | SPLIT).halo == 0
+    assert ops.conv_engine_plan("conv", 1, 64, 9, 26, 64, 3, 1, 1,
+                                layout=1 | SPLIT | _lib.CONV_EXACT_F32).halo == 0
+
+
+def test_engine_plan_contraction_and_chunks():
+    """C % 32 == 16 with a split pack and NCHW input: guarded (zero-padded) chunks on the split
+    contraction (full 0, prec 1); the same on exact f32 or with a plain pack is 16-channel full
+    chunks (cfg 1) in exact f32.  The DCN's chunk configurations; the tail's layouts."""
+    for c in (48, 80):
+        p = ops.conv_engine_plan("conv", 2, c, 24, 52, 64, 3, 1, 1, layout=SPLIT)
+        assert (p.status, p.full, p.cfg, p.prec, p.layout) == (0, 0, 0, 1, 0), p
+        p = ops.conv_engine_plan("conv", 2, c, 24, 52, 64, 3, 1, 1, layout=SPLIT | _lib.CONV_EXACT_F32)
+        assert (p.status, p.full, p.cfg, p.prec, p.ptt) == (0, 1, 1, 0, 128), p
+    p = ops.conv_engine_plan("dcn", 2, 64, 16, 52, 64, 3, 1, 2, 2, deformable_groups=2, layout=SPLIT)
+    assert (p.status, p.full, p.cfg, p.prec, p.ptt) == (0, 1, 0, 1, 64)
+    p = ops.conv_engine_plan("dcn", 2, 32, 16, 52, 32, 3, 1, 2, 2, deformable_groups=2, layout=SPLIT)
+    assert (p.status, p.full, p.cfg, p.prec, p.co_t) == (0, 1, 2, 0, 32)
+    p = ops.conv_engine_plan("dcn", 2, 64, 16, 52, 64, 3, 1, 2, 2, deformable_groups=2, packed=False)
+    assert (p.status, p.full, p.prec, p.packed) == (0, 1, 0, 0)
+    for layout in (0, 1):
+        p = ops.conv_engine_plan("conv", 2, 64, 25, 36, 64, 3, 2, 1, co2=64, layout=layout | SPLIT)
+        assert (p.status, p.tail, p.layout, p.prec, p.halo) == (0, 1, layout, 1, 0)
+    # the tail's tile covers max(co, co2)
+    assert ops.conv_engine_plan("conv", 2, 32, 9, 26, 16, 3, 1, 1, co2=32).co_t == 32
+
+
+def test_engine_plan_refusals_match_the_launch_without_a_gpu():
+    """What launch_fwd refuses comes back from the plan with the same status, and -- for the
+    shapes an entry point can express -- from the entry point itself (dummy pointers: the
+    refusal comes before any launch)."""
+    import ctypes as C
+    U, E = _lib.EUNSUPPORTED, -1
+    plan = ops.conv_engine_plan
+    assert plan("conv", 1, 64, 8, 8, 128, 3, 1, 1, co2=64).status == U        # tail with Co > 64
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, co2=65).status == U         # ... or Co2 > 64
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, co2=64, packed=False).status == U
+    assert plan("conv", 1, 24, 8, 8, 32, 3, 1, 1, layout=1).status == U       # NHWC, 24 channels
+    assert plan("conv", 1, 16, 8, 8, 16, 3, 1, 1, layout=1).status == U       # 16-ch chunks, co_t 16
+    assert plan("conv", 1, 64, 8, 8, 54, 3, 1, 1, groups=2, layout=2).status == U   # Cog % 4
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, co2=64, layout=2).status == U     # NHWC out + tail
+    assert plan("conv", 1, 64, 8, 10, 64, 3, 1, 1, co2=64, csa=[(4, 5)]).status == U   # CSA, Wo % 4
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, co2=64, csa=[(4, 4)]).status == 0
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, co2=64, csa=[(3, 3)]).status == U    # not 2x / 4x
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, co2=64, csa=[(4, 4), (2, 2), (1, 1)]).status == U
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, csa=[(4, 4)]).status == U            # CSA, no tail
+    assert plan("dcn", 1, 64, 8, 1, 64, 3, 1, 1, deformable_groups=2).status == U      # DCN, W < 2
+    assert plan("dcn", 1, 64, 8, 2, 64, 3, 1, 1, deformable_groups=2).status == 0
+    # the post stage has one form: HALO 1 tail (split, NHWC input, dil 1) with CSA, 64 -> 64
+    post = dict(co2=64, csa=[(4, 4)], layout=1 | SPLIT)
+    ok = plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, post=1, **post)
+    assert (ok.status, ok.post, ok.halo, ok.tail) == (0, 1, 1, 1)
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, post=2, **post).status == U          # disp / skip
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 2, 2, post=1, **post).status == U       # dil 2
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, post=1, co2=64, csa=[(4, 4)], layout=1).status == U
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, post=1, co2=64, layout=1 | SPLIT).status == U
+    assert plan("dcn", 1, 64, 8, 8, 64, 3, 1, 1, deformable_groups=2, post=1, **post).status == U
+    # invalid sizes
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 0, 1).status == E                 # stride 0
+    assert plan("conv", 1, 63, 8, 8, 64, 3, 1, 1, groups=2).status == E
+    assert plan("conv", 1, 64, 2, 8, 64, 5, 1, 0).status == E                 # no output rows
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, layout=4).status == E
+    assert plan("conv", 1, 64, 8, 8, 64, 3, 1, 1, layout=_lib.CONV_GENERIC_DCN).status == E
+    assert plan("conv", 1, 1 << 16, 128, 128, 64, 1).status == U              # 2^31-byte planes
+    # ... and the same from the entry points
+    L = _lib.lib()
+    p = C.c_void_p(16)
+    fused = lambda *shape: L.aanet_conv2d_fused_f32(p, p, None, None, None, None, 0, 1, p, *shape, None)  # noqa: E731
+    assert fused(1, 24, 8, 8, 32, 3, 3, 1, 1, 1, 1, 1) == U
+    assert fused(1, 64, 8, 8, 54, 3, 3, 1, 1, 1, 2, 2) == U
+    assert fused(1, 64, 8, 8, 64, 3, 3, 1, 1, 1, 1, 4) == E
+    assert fused(1, 64, 8, 8, 64, 3, 3, 0, 1, 1, 1, 0) == E                   # stride 0: no SIGFPE
+    pw = lambda co, co2, w, desc: L.aanet_conv2d_pw_f32(  # noqa: E731
+        p, p, None, None, None, 0, p, None, None, 0, co2, p, 1, 64, 8, w, co, 3, 3, 1, 1, 1, desc, 0, None)
+    assert pw(128, 64, 8, None) == U
+    d = _lib.CsaEpilogue()
+    d.out, d.num_up = 16, 1
+    d.up[0], d.up_h[0], d.up_w[0] = 16, 4, 5
+    assert pw(64, 64, 10, C.byref(d)) == U
+    assert L.aanet_mdcn_fwd_f32(p, p, p, p, None, p, 1, 64, 8, 1, 64, 3, 3, 1, 1, 1, 1, 2, None) == U
+
+
+def test_engine_plan_descriptor_sizes_are_checked():
+    import ctypes as C
+    L = _lib.lib()
+    q, pl = _lib.ConvPlanQuery(), _lib.ConvPlan()
+    assert q.struct_size == C.sizeof(q) and pl.struct_size == C.sizeof(pl)
+    assert L.aanet_conv_engine_plan(None, C.byref(pl)) == -1
+    q.struct_size -= 4
+    assert L.aanet_conv_engine_plan(C.byref(q), C.byref(pl)) == _lib.EABI
+    q.struct_size += 4
+    pl.struct_size = 8
+    assert L.aanet_conv_engine_plan(C.byref(q), C.byref(pl)) == _lib.EABI
+    with pytest.raises(_lib.AanetError):
+        _lib.call("aanet_conv_engine_plan", C.byref(q), C.byref(pl))
+
+
+def test_nhwc_assembly_refuses_more_than_496_channels_without_a_gpu():
+    """aanet_concat_nhwc_f32 / aanet_deconv2x_assemble_nhwc_f32 stage every channel of 64 (up to
+    252 channels) or 32 (up to 496) output columns in 64 KiB of LDS: 497 channels come back as
+    AANET_EUNSUPPORTED from the host, before any launch (dummy pointers)."""
+    import ctypes as C
+    L = _lib.lib()
+    p = C.c_void_p(16)
+    assert 496 * 33 * 4 <= 64 * 1024 < 497 * 33 * 4 and 252 * 65 * 4 <= 64 * 1024 < 253 * 65 * 4
+    assert L.aanet_concat_nhwc_f32(p, p, p, 2, 200, 297, 4, 10, None) == _lib.EUNSUPPORTED
+    assert L.aanet_deconv2x_assemble_nhwc_f32(p, p, p, 2, 249, 248, 4, 10, None) == _lib.EUNSUPPORTED
+    assert L.aanet_concat_nhwc_f32(p, p, p, 2, 200, 296, 5, 10, None) == _lib.EUNSUPPORTED  # odd h

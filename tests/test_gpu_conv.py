@@ -132,7 +132,15 @@ def test_csa_sum_vs_torch_interpolate(sizes, act):
     assert err <= 2e-5 * (1 + ref.abs().max().item()), err
 
 
-@pytest.mark.parametrize("C,H,W", [(64, 16, 52), (32, 9, 26), (16, 5, 13), (48, 7, 30)])
+# tail tables (N = 2, 3x3 stride 1; also read by the engine census, tests/test_engine_census.py)
+PW_TAIL_CASES = [(64, 16, 52), (32, 9, 26), (16, 5, 13), (48, 7, 30), (64, 9, 26)]
+MDCN_TAIL_CASES = [(64, 16, 52), (32, 9, 26), (16, 5, 13)]
+PW_TAIL_NHWC_CASES = [(64, 16, 52), (64, 9, 26)]
+MDCN_TAIL_NHWC_CASES = [(64, 16, 52, 1.0, 2), (64, 9, 26, 3.0, 2), (32, 7, 19, 1.0, 1), (32, 9, 26, 1.5, 2),
+                        (64, 6, 17, 2.0, 4)]
+
+
+@pytest.mark.parametrize("C,H,W", PW_TAIL_CASES)
 def test_conv2d_pw_tail_vs_torch_cpu(C, H, W):
     """conv3x3 + BN + ReLU -> 1x1 conv + BN + identity + ReLU (SimpleBottleneck tail) in one kernel."""
     gen = torch.Generator().manual_seed(C)
@@ -151,7 +159,7 @@ def test_conv2d_pw_tail_vs_torch_cpu(C, H, W):
     assert err <= 3e-5 * (1 + ref.abs().max().item()), err
 
 
-@pytest.mark.parametrize("C,H,W", [(64, 16, 52), (32, 9, 26), (16, 5, 13)])
+@pytest.mark.parametrize("C,H,W", MDCN_TAIL_CASES)
 def test_mdcn_pw_tail_vs_oracle(C, H, W):
     """DeformSimpleBottleneck tail: DCN (+BN2+ReLU, mask = 2*sigmoid) -> conv3 + BN3 + identity + ReLU."""
     import numpy as np
@@ -188,6 +196,7 @@ NHWC_CASES = [
     (1, 128, 5, 11, 40, 3, 1, 1, 1, 4),      # 4 groups of 32, Co not a tile multiple
     (2, 32, 9, 26, 54, 3, 1, 2, 2, 2),       # scale-1 offset_conv: 16-channel groups (CFG 1)
     (1, 64, 7, 20, 80, 3, 1, 1, 1, 4),       # 16-channel groups, Cog 20
+    (1, 64, 9, 27, 64, 3, 2, 1, 1, 1),       # strided, 64-channel tile, ragged last tile (70 px)
 ]
 
 
@@ -233,7 +242,7 @@ def test_conv2d_nhwc_requires_full_chunks():
         ops.conv2d_fused(x, w, None, 1, 1, 1, 1, packed_weight=ops.pack_weight(w))
 
 
-@pytest.mark.parametrize("C,H,W", [(64, 16, 52), (64, 9, 26)])
+@pytest.mark.parametrize("C,H,W", PW_TAIL_NHWC_CASES)
 def test_conv2d_pw_tail_nhwc_input(C, H, W):
     gen = torch.Generator().manual_seed(C + H)
     N = 2
@@ -252,9 +261,7 @@ def test_conv2d_pw_tail_nhwc_input(C, H, W):
     assert err <= 3e-5 * (1 + ref.abs().max().item()), err
 
 
-@pytest.mark.parametrize("C,H,W,off_scale,dg", [(64, 16, 52, 1.0, 2), (64, 9, 26, 3.0, 2),
-                                                (32, 7, 19, 1.0, 1), (32, 9, 26, 1.5, 2),
-                                                (64, 6, 17, 2.0, 4)])
+@pytest.mark.parametrize("C,H,W,off_scale,dg", MDCN_TAIL_NHWC_CASES)
 def test_mdcn_pw_tail_nhwc_input_vs_oracle(C, H, W, off_scale, dg):
     """DCN with NHWC corner loads (+BN2+ReLU, mask = 2*sigmoid) -> conv3 + identity + ReLU.
     dg with 16-channel groups: chunks span two groups, one sampling state each (CFG 2)."""

@@ -29,7 +29,7 @@ def _errs(got, ref64, scale64):
     return e.max().item(), e.mean().item(), (e / (scale64 + 1e-30)).max().item()
 
 
-@pytest.mark.parametrize("case", [
+SPLIT_CASES = [  # also read by the engine census (tests/test_engine_census.py)
     # N, C, H, W, Co, k, stride, pad, dil, groups, nhwc
     (2, 64, 24, 52, 64, 3, 1, 1, 1, 1, True),     # SimpleBottleneck conv2 (NHWC staging)
     (2, 64, 24, 52, 64, 3, 1, 1, 1, 1, False),    # same, NCHW staging
@@ -48,7 +48,15 @@ def _errs(got, ref64, scale64):
     (2, 48, 25, 36, 64, 3, 2, 1, 1, 1, False),    # conv2a: stride 2, ragged
     (1, 48, 13, 30, 128, 2, 1, 1, 1, 1, False),   # deconv1 phase conv: 2x2 pad 1, two co tiles
     (1, 80, 9, 20, 32, 3, 1, 1, 1, 1, False),     # three chunks, the last half empty
-])
+    # two groups of 48 channels (C = 96): the zero-padded pack with a group stride, ragged H, W
+    (2, 96, 23, 37, 64, 3, 1, 1, 1, 2, False),    # 3x3 stride 1
+    (2, 96, 23, 37, 128, 3, 2, 1, 1, 2, False),   # 3x3 stride 2, 64 outputs per group
+    # halo tile, one chunk, 32-channel tile (as the exact-fit case above) with ragged rows / columns
+    (1, 32, 9, 20, 32, 3, 1, 1, 1, 1, True),
+]
+
+
+@pytest.mark.parametrize("case", SPLIT_CASES)
 def test_split_conv_accuracy_vs_fp64(case):
     N, C, H, W, Co, k, s, p, d, g, nhwc = case
     gen = torch.Generator().manual_seed(7)
@@ -127,10 +135,8 @@ def test_split_tail_kernels_match_exact(dcn):
         assert (a - e).abs().max().item() <= 2e-5 * (1 + e.abs().max().item())
 
 
-def test_split_pack_reconstructs_weights_exactly():
-    """Head of the buffer = pack_weight (bit-exact); pieces h + m + l == w exactly."""
+def _check_split_pack(Co, Cg, k, g):
     gen = torch.Generator(device=DEV).manual_seed(5)
-    Co, Cg, k, g = 54, 32, 3, 2
     w = torch.randn(Co, Cg, k, k, device=DEV, generator=gen) * 0.3
     ws = ops.pack_weight_split(w, g)
     assert torch.equal(ws, ops.pack_weight(w))
@@ -139,18 +145,30 @@ def test_split_pack_reconstructs_weights_exactly():
     frag = buf[off:].view(np.uint16).reshape(-1, 3, 64, 8)  # (g, t, k, cc, blk) x piece x lane x 8
     f32 = lambda u: (u.astype(np.uint32) << 16).view(np.float32).astype(np.float64)  # noqa: E731
     total = f32(frag[:, 0]) + f32(frag[:, 1]) + f32(frag[:, 2])
-    Cog, T, NCC, K = Co // g, 1, Cg // 32, k * k
+    Cog, K = Co // g, k * k
+    T, NCC = (Cog + 63) // 64, (Cg + 31) // 32
     wn = w.cpu().numpy().astype(np.float64)
     total = total.reshape(g, T, K, NCC, 4, 64, 8)
-    for gi in range(g):
-        for kk in range(K):
-            for blk in range(4):
-                for lane in range(64):
-                    row = 16 * blk + (lane & 15)
-                    for j in range(8):
-                        c = 8 * (lane >> 4) + j
-                        want = wn[gi * Cog + row, c, kk // k, kk % k] if row < Cog else 0.0
-                        assert total[gi, 0, kk, 0, blk, lane, j] == want
+    # want[g][t][k][cc][blk][lane][j] = w[g Cog + 64 t + 16 blk + lane % 16][32 cc + 8 (lane / 16) + j][k]
+    # inside the group's rows and channels, else 0
+    wpad = np.zeros((g, T * 64, NCC * 32, K))
+    wpad[:, :Cog, :Cg] = wn.reshape(g, Cog, Cg, K)
+    want = wpad.reshape(g, T, 4, 16, NCC, 4, 8, K)          # g t blk r cc q j k
+    want = want.transpose(0, 1, 7, 4, 2, 5, 3, 6)            # g t k cc blk q r j
+    assert np.array_equal(total, want.reshape(g, T, K, NCC, 4, 64, 8))
+
+
+def test_split_pack_reconstructs_weights_exactly():
+    """Head of the buffer = pack_weight (bit-exact); pieces h + m + l == w exactly."""
+    _check_split_pack(54, 32, 3, 2)
+
+
+@pytest.mark.parametrize("Co,Cg,k,g", [(64, 48, 3, 2), (128, 48, 3, 2), (140, 48, 2, 2)])
+def test_split_pack_reconstructs_padded_groups_exactly(Co, Cg, k, g):
+    """The same for two groups of 48 channels: two chunks per group, the second zero past channel
+    47 (the zero-padded pack of test_split_conv_accuracy_vs_fp64's C = 96 cases); Co = 140: two
+    64-row tiles per group, the second ragged (rows 70 .. 127 zero)."""
+    _check_split_pack(Co, Cg, k, g)
 
 
 def test_split_unsupported_shapes_fall_back():
