@@ -29,6 +29,13 @@ __device__ __forceinline__ f32x4 mfma16x16x4(float a, float b, f32x4 c) {
 
 __device__ __forceinline__ int div_up(int a, int b) { return (a + b - 1) / b; }
 
+// activation of every fused epilogue: 0 identity, 1 relu, 2 leaky(0.2).  Branch-free in the
+// wave-uniform act (selects, not scalar branches that split the epilogue into per-value blocks)
+__device__ __forceinline__ float act_f(float v, int act) {
+  const float neg = act == 2 ? 0.2f * v : (act == 1 ? 0.f : v);
+  return v > 0.f ? v : neg;
+}
+
 // ---- split-bf16 activations: two fp32 values -> their three exact bf16 pieces each, x = h + m + l,
 // by truncation: h = the upper 16 bits of x, r = x - h (exact, <= 16 significant bits), m = the
 // upper 16 bits of r, l = r - m (exact, <= 8 significant bits, so its upper half IS its bf16

@@ -30,11 +30,6 @@ constexpr int CG = 8;          // channels per deformable group
 constexpr int CT = 16;         // channels = Co (= Co2)
 constexpr int EW = 4;          // epilogue waves (CT / EW output channels each)
 
-__device__ __forceinline__ float act_f(float v, int act) {
-  const float neg = act == 2 ? 0.2f * v : (act == 1 ? 0.f : v);
-  return v > 0.f ? v : neg;
-}
-
 struct Samp {
   unsigned o[4];  // corner byte offsets within a channel plane (out of range: corner invalid)
   float w[4];     // corner weights, mask folded

@@ -26,8 +26,9 @@
 // Numerics are those of the generic engine: corner positions, validity and weights follow
 // kernel.cu:467-497 / make_samp4 bit for bit (fp contraction off); the blend is
 // ((c0 w0 + c1 w1) + c2 w2) + c3 w3 with the mask folded into the weights; the contraction is the
-// split-bf16 one (three exact bf16 pieces, six products, fp32 accumulation; mdcn.hip split3).
+// split-bf16 one (three exact bf16 pieces, six products, fp32 accumulation; split.h).
 #include "dcn_tile.h"
+#include "split.h"
 
 #include <cstdio>
 
@@ -35,8 +36,6 @@
 
 namespace {
 
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
@@ -47,42 +46,10 @@ constexpr int RW = 2;            // window margin beyond the taps: offsets in [-
 constexpr int K = 9;             // 3x3 taps
 constexpr int OP = TR * TC + 4;  // epilogue tile pitch (floats)
 
-// ---- split-bf16 contraction (same scheme as mdcn.hip split3 / mfma_split6) -------------------
-// 8 values -> their three exact bf16 pieces (x = h + m + l; common.h split_pair)
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8 (&b)[3]) {
-  u32x4 hh, mm, ll;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    unsigned h, m, l;
-    split_pair(v[2 * i], v[2 * i + 1], h, m, l);
-    hh[i] = h;
-    mm[i] = m;
-    ll[i] = l;
-  }
-  b[0] = __builtin_bit_cast(bf16x8, hh);
-  b[1] = __builtin_bit_cast(bf16x8, mm);
-  b[2] = __builtin_bit_cast(bf16x8, ll);
-}
-__device__ __forceinline__ f32x4 mfma_split6(const bf16x8 (&A)[3], const bf16x8 (&B)[3], f32x4 t) {
-  t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[1], B[1], t, 0, 0, 0);
-  t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B[2], t, 0, 0, 0);
-  t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[2], B[0], t, 0, 0, 0);
-  t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B[1], t, 0, 0, 0);
-  t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[1], B[0], t, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[0], B[0], t, 0, 0, 0);
-}
-
 // the resource of an optional tensor's image planes: an absent tensor gets 0 records (its loads
 // return 0, its stores are dropped), on any valid base
 __device__ __forceinline__ brsrc_t opt_rsrc(const float *p, const float *any, long img, long bytes) {
   return buf_rsrc(p ? p + img : any, p ? bytes : 0);
-}
-
-// branch-free in the wave-uniform act (selects, not scalar branches that split the epilogue
-// into per-value basic blocks); same values as relu / leaky(0.2) / identity
-__device__ __forceinline__ float act_f(float v, int act) {
-  const float neg = act == 2 ? 0.2f * v : (act == 1 ? 0.f : v);
-  return v > 0.f ? v : neg;
 }
 
 // Sampling state of one (pixel, tap, deformable group): the window position of the top-left

@@ -20,11 +20,6 @@ namespace {
 constexpr int NT = 256;
 constexpr int TY = 8, TX = 32;  // output tile: 8 rows x 32 columns, one pixel per thread
 
-__device__ __forceinline__ float act_f(float v, int act) {
-  const float neg = act == 2 ? 0.2f * v : (act == 1 ? 0.f : v);
-  return v > 0.f ? v : neg;
-}
-
 template <int CIN, int KS, int S, int CO_T, bool NHWC_IN>
 __global__ __launch_bounds__(NT) void conv_direct_kernel(DirectArgs a) {
   constexpr int IR = (TY - 1) * S + KS, IC = (TX - 1) * S + KS;  // input tile (dilation 1)

@@ -768,7 +768,7 @@ DCN_BWD_ALGOS = {"auto": 0, "global": 1, "window": 2}  # AANET_DCN_BWD_* (includ
 
 
 def window_bwd_ok(C, Co, kh, kw, stride, dilation, deformable_groups):
-    """Whether AANET_DCN_BWD_WINDOW takes a DCN backward shape (mdcn.hip win_shape_ok; the full
+    """Whether AANET_DCN_BWD_WINDOW takes a DCN backward shape (mdcn_bwd.hip win_shape_ok; the full
     list of include/aanet_mi355x.h).  The LDS term: gOut tile, W^T slice, sampling / partial
     buffers, sampled columns and the int64 window of (7 s + 1 + (k-1) dil + 4)^2 positions x 16
     channels, within the CU's 160 KiB."""
@@ -776,7 +776,7 @@ def window_bwd_ok(C, Co, kh, kw, stride, dilation, deformable_groups):
     if stride not in (1, 2) or cpg > 128 or C % 4 or cpg % 4 or kh * kw > 9 or Co > 128 or Co % 16:
         return False
     pitch = lambda v: v + (2 - v % 32) % 32  # noqa: E731  (mdcn.hip round_pitch(v, 2))
-    # mdcn.hip win_rows: 7 * stride + 1 rows under an 8-pixel tile + the taps' reach + 2 x 2
+    # mdcn_bwd.hip win_rows: 7 * stride + 1 rows under an 8-pixel tile + the taps' reach + 2 x 2
     wr, wc = 7 * stride + 1 + (kh - 1) * dilation + 4, 7 * stride + 1 + (kw - 1) * dilation + 4
     smem = 4 * (Co * pitch(64) + 16 * pitch(Co) + 16 * 66 + 64 * 16 + 3 * 9 * 64 + 16 * 66) \
         + wr * wc * 16 * 8

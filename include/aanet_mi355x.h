@@ -313,7 +313,7 @@ int aanet_conv_weight_pack_dgrad_f32(const float *weight, float *weight_packed, 
 
 /* Weight buffer for the split-bf16 contraction (AANET_CONV_WEIGHTS_SPLIT): the
  * aanet_conv_weight_pack_f32 layout, then (at a 256-byte aligned offset) every weight split into
- * three bf16 pieces and laid out as MFMA operand fragments (mdcn.hip, split_frag_offset).
+ * three bf16 pieces and laid out as MFMA operand fragments (split.h, split_frag_offset).
  * weight is the reference layout [co][cg][kh][kw] of a conv with `groups` groups; needs
  * cg % 32 == 0.  _bytes returns the buffer size, 0 when unsupported. */
 long aanet_conv_weight_pack_split_bytes(int co, int cg, int kh, int kw, int groups);

@@ -7,7 +7,7 @@ TAG=$1; EXTRA=$2
 R=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
 mkdir -p "$T/aanet_amd" "$T/include"
-cp -r "$R/aanet_amd/csrc" "$T/aanet_amd/"; cp "$R/include/"*.h "$T/include/"
+cp -a "$R/aanet_amd/csrc" "$T/aanet_amd/"; cp -p "$R/include/"*.h "$T/include/"  # keep mtimes: ONLY= reuses objects
 # ONLY=<src.hip>: reuse the product objects and recompile just that source with the extra flags
 if [ -n "$ONLY" ]; then touch "$T/aanet_amd/csrc/$ONLY"; else rm -rf "$T/aanet_amd/csrc/build"; fi
 make -s -C "$T/aanet_amd/csrc" -j8 LIB="$R/aanet_amd/libaanet_mi355x_$TAG.so" \
