@@ -58,6 +58,9 @@ _SIGNATURES = {
     "aanet_conv3x3s2_terms_f32": [_P, _P, _P] + [_I] * 6 + [_P, _I, _P, _I, _P, _P],
     "aanet_conv3x3_grouped_pack_f32": [_P, _I, _I, _I, _P, _P],
     "aanet_conv3x3_grouped_nhwc_f32": [_P, _P, _P] + [_I] * 7 + [_P, _P],
+    "aanet_conv3d_pack_f32": [_P, _I, _I, _P, _P],
+    "aanet_conv3d_fused_f32": [_P, _P, _P, _P, _I, _P] + [_I] * 6 + [_P],
+    "aanet_conv3d_supported": [_I] * 9,
     "aanet_mdcn_im2col_f32": [_P, _P, _P, _P] + [_I] * 9 + [_P],
     "aanet_mdcn_sample_index": [_P, _P, _P, _P] + [_I] * 9 + [_P],
     "aanet_conv_engine_plan": [_P, _P],
@@ -73,6 +76,7 @@ _SIZE_FUNCTIONS = [
     ("aanet_conv3x3s2_pack_bytes", [_I, _I], ctypes.c_size_t),
     ("aanet_conv3x3_grouped_pack_bytes", [_I, _I, _I], ctypes.c_size_t),
     ("aanet_mdcn_window_fwd_supported", [_I] * 10, _I),
+    ("aanet_conv3d_pack_bytes", [_I, _I], ctypes.c_size_t),
 ]
 
 _lib = None
@@ -137,6 +141,12 @@ def is_nhwc(t):
     """channels_last 4-D tensor that is not also NCHW-contiguous (physical layout NHWC)."""
     return (t is not None and t.dim() == 4 and not t.is_contiguous()
             and t.is_contiguous(memory_format=torch.channels_last))
+
+
+def is_ndhwc(t):
+    """channels_last_3d 5-D tensor (physical layout NDHWC; a tensor that is also NCDHW-contiguous,
+    e.g. one channel or a 1x1x1 volume, has the same bytes in both and counts)."""
+    return t is not None and t.dim() == 5 and t.is_contiguous(memory_format=torch.channels_last_3d)
 
 
 LAYOUT_IN_NHWC, LAYOUT_OUT_NHWC = 1, 2  # AANET_LAYOUT_* (include/aanet_mi355x.h)

@@ -1,0 +1,277 @@
+// conv3d.hip -- the 3-D aggregators' eval convs (nets/aggregation.py:8-21, 52-67: Conv3d 3x3x3,
+// stride 1, padding 1, dilation 1, one group, BN folded by the caller) for gfx950:
+//   out = act(conv3d(x, W) + bias [+ residual]),  x / residual / out channels-last [n][d][h][w][c].
+//
+// Depth marching.  A workgroup (4 waves) owns an 8 x 16 (h x w) output tile of one image and one
+// block of 32 output channels (grid.y), and walks the input planes d_in = 0 .. D-1.  For every
+// plane and 32-channel chunk the tile's 10 x 18 halo is loaded once, split into its three bf16
+// pieces once and stored in LDS (34.5 KB, the XOR-swizzled 64-byte rows of the 2-D halo forms:
+// conflict-free ds_read_b128 for any tap shift); the next plane's loads are in flight in registers
+// while this one is contracted.  The staged plane feeds all 27 taps: the B fragment of in-plane
+// tap (ti, tj) serves kd = 2, 1, 0, i.e. the output planes d_in-1, d_in, d_in+1, which are three
+// rolling accumulator sets; plane d_in-1 is complete, and stored, once plane d_in is consumed.
+// Depth padding is planes that are never staged; h / w padding is the zero a buffer load returns
+// past its range.  Every input element is staged and split once per workgroup and output-channel
+// block (1.4x for the halo), against 3x for a 2-D tiling with kd outside and 27x for an im2col.
+//
+// Wave w owns tile rows w and w + 4: lane (kr = lane / 16, jj = lane % 16) = column jj, channels
+// 8kr..8kr+7 of the B fragment.  An A fragment (pre-split weights, streamed from L2 / L1 -- the
+// four waves read the same lines) feeds both rows, so a step of 27 taps is 162 16-byte A loads,
+// 54 ds_read_b128 and 648 MFMAs per wave.
+//
+// Addressing: one buffer resource per image (64-bit base per n), 32-bit byte offsets inside the
+// image's volume; the entry point refuses volumes of 2^31 bytes per image.
+//
+// Numerics: the split-bf16 contraction of split.h (six piece products, fp32 accumulation); per
+// output the order is input plane, chunk, in-plane tap ascending -- independent of the batch.
+#include <hip/hip_runtime.h>
+
+#include "common.h"
+#include "split.h"
+
+namespace {
+
+constexpr int NT = 256;                     // 4 waves, two tile rows each
+constexpr int TR = 8, TC = 16;              // output tile (h x w)
+constexpr int HWW = TC + 2, HR = TR + 2;    // halo
+constexpr int NPOS = HR * HWW;              // 180 positions
+constexpr int PE = NPOS * 32;               // bf16 per piece plane
+constexpr int HIT = (NPOS * 4 + NT - 1) / NT;  // halo octets (8 channels of a position) per thread
+constexpr unsigned OOB = 0x80000000u;
+
+struct C3Args {
+  const float *x;      // [N][D][H][W][C]
+  const bf16x8 *wsplit;  // [Co/32][C/32][9 (kh,kw)][3 kd][2 co blocks][3 pieces][64 lanes] x 16 B
+  const float *bias;   // [Co] or NULL
+  const float *res;    // [N][D][H][W][Co] or NULL
+  float *out;          // [N][D][H][W][Co]
+  int N, C, D, H, W, Co, act;
+};
+
+// bf16 offset of 16-byte slot q8 (channels 8 q8 .. 8 q8 + 7) of halo position pos (conv_g3.hip)
+__device__ __forceinline__ int c3_swz(int pos, int q8) {
+  return pos * 32 + ((q8 ^ (((pos >> 2) & 1) << 1)) << 3);
+}
+
+__global__ __launch_bounds__(NT, 2) void conv3d_kernel(C3Args a) {
+  __shared__ __attribute__((aligned(16))) __bf16 sH[3 * PE];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kr = lane >> 4, jj = lane & 15;
+  const int C = a.C, D = a.D, H = a.H, W = a.W, Co = a.Co;
+  const int tx = (W + TC - 1) / TC, ntiles = tx * ((H + TR - 1) / TR);
+  const int n = blockIdx.x / ntiles, tile = blockIdx.x % ntiles, cb = blockIdx.y;
+  const int y0 = (tile / tx) * TR, x0 = (tile % tx) * TC;
+  const int ncc = C / 32;
+  const long in_img = (long)D * H * W * C, out_img = (long)D * H * W * Co;  // elements, < 2^29
+  const brsrc_t xr = buf_rsrc(a.x + n * in_img, in_img * 4);
+  const brsrc_t orr = buf_rsrc(a.out + n * out_img, out_img * 4);
+  const unsigned in_plane = (unsigned)(H * W * C) * 4u;  // bytes
+
+  // halo item i of this thread: position e >> 2, channel octet e & 3; its byte offset inside a
+  // plane's chunk 0, or OOB outside the image (the range check then returns zeros: the padding)
+  unsigned hoff[HIT];
+#pragma unroll
+  for (int i = 0; i < HIT; ++i) {
+    const int e = tid + NT * i, pos = e >> 2;
+    const int yy = y0 - 1 + pos / HWW, xx = x0 - 1 + pos % HWW;
+    const bool ok = pos < NPOS && yy >= 0 && yy < H && xx >= 0 && xx < W;
+    hoff[i] = ok ? (unsigned)(((yy * W + xx) * C + 8 * (e & 3)) * 4) : OOB;
+  }
+  f32x4 hv[HIT][2];
+  auto load_halo = [&](int d, int cc) {
+    const unsigned uni = (unsigned)d * in_plane + 128u * (unsigned)cc;  // < 2^31: OOB stays out of range
+#pragma unroll
+    for (int i = 0; i < HIT; ++i) {
+      hv[i][0] = buf_ld4(xr, hoff[i] + uni);
+      hv[i][1] = buf_ld4(xr, hoff[i] + uni + 16u);
+    }
+  };
+  auto store_halo = [&]() {
+#pragma unroll
+    for (int i = 0; i < HIT; ++i) {
+      const int e = tid + NT * i, pos = e >> 2;
+      if (pos < NPOS) {
+        const float v[8] = {hv[i][0][0], hv[i][0][1], hv[i][0][2], hv[i][0][3],
+                            hv[i][1][0], hv[i][1][1], hv[i][1][2], hv[i][1][3]};
+        bf16x8 b[3];
+        split8(v, b);
+        const int o = c3_swz(pos, e & 3);
+#pragma unroll
+        for (int pc = 0; pc < 3; ++pc) *reinterpret_cast<bf16x8 *>(sH + pc * PE + o) = b[pc];
+      }
+    }
+  };
+
+  // acc[s][r][m]: output plane d_in - 1 + s, tile row wave + 4r, channels 32cb + 16m + 4kr + 0..3
+  f32x4 acc[3][2][2];
+#pragma unroll
+  for (int s = 0; s < 3; ++s)
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int m = 0; m < 2; ++m) acc[s][r][m] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // epilogue of one finished plane: bias, residual, activation, NDHWC channel-quad stores; pixels
+  // past the image get an offset the range check drops
+  f32x4 bv[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+  if (a.bias) {
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) bv[m][u] = a.bias[32 * cb + 16 * m + 4 * kr + u];
+  }
+  const float *resp = a.res ? a.res + n * out_img : a.out + n * out_img;  // a valid base either way
+  const brsrc_t rr = buf_rsrc(resp, out_img * 4);
+  const bool has_res = a.res != nullptr;
+  const int act = a.act;
+  auto store_plane = [&](int dz, const f32x4 (&ac)[2][2]) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int y = y0 + wave + 4 * r, x = x0 + jj;
+      const bool ok = y < H && x < W;
+      const unsigned pix = (unsigned)(((dz * H + y) * W + x) * Co + 32 * cb + 4 * kr) * 4u;
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        const unsigned off = ok ? pix + 64u * m : OOB;
+        f32x4 v = ac[r][m] + bv[m];
+        if (has_res) v += buf_ld4(rr, off);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = act_f(v[u], act);
+        buf_st4(orr, off, v);
+      }
+    }
+  };
+
+  load_halo(0, 0);
+  for (int d = 0; d < D; ++d) {
+    for (int cc = 0; cc < ncc; ++cc) {
+      __syncthreads();  // every wave is done reading the previous halo
+      store_halo();
+      __syncthreads();
+      if (cc + 1 < ncc)
+        load_halo(d, cc + 1);
+      else if (d + 1 < D)
+        load_halo(d + 1, 0);
+      const bf16x8 *wb = a.wsplit + ((long)(cb * ncc + cc) * (27 * 6)) * 64 + lane;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        const int ti = k / 3, tj = k % 3;
+        bf16x8 B[2][3];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const __bf16 *bp = sH + c3_swz((wave + 4 * r + ti) * HWW + jj + tj, kr);
+#pragma unroll
+          for (int pc = 0; pc < 3; ++pc) B[r][pc] = *reinterpret_cast<const bf16x8 *>(bp + pc * PE);
+        }
+#pragma unroll
+        for (int kd = 0; kd < 3; ++kd)
+#pragma unroll
+          for (int m = 0; m < 2; ++m) {
+            bf16x8 A[3];
+#pragma unroll
+            for (int pc = 0; pc < 3; ++pc) A[pc] = wb[(((k * 3 + kd) * 2 + m) * 3 + pc) * 64];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) acc[2 - kd][r][m] = mfma_split6(A, B[r], acc[2 - kd][r][m]);
+          }
+      }
+    }
+    if (d >= 1) store_plane(d - 1, acc[0]);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        acc[0][r][m] = acc[1][r][m];
+        acc[1][r][m] = acc[2][r][m];
+        acc[2][r][m] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+  }
+  store_plane(D - 1, acc[0]);
+}
+
+// w [Co][C][3][3][3] fp32 -> [Co/32][C/32][9 (kh,kw)][3 kd][2][3 pieces][64 lanes][8 bf16]: lane l
+// of co block m holds row 32cb + 16m + l%16, channels 32cc + 8(l/16) + 0..7, as three bf16 pieces
+// (round to nearest: h = bf16(x), m = bf16(x - h), l = bf16(x - h - m))
+__global__ void conv3d_pack_kernel(const float *__restrict__ w, bf16x8 *__restrict__ out, int Co, int C) {
+  const int ncc = C / 32, total = (Co / 32) * ncc * 27 * 2 * 64;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+    const int l = e & 63, m = (e >> 6) & 1;
+    int r = e >> 7;
+    const int kd = r % 3;
+    r /= 3;
+    const int k = r % 9;
+    r /= 9;
+    const int cc = r % ncc, cb = r / ncc;
+    const int co = 32 * cb + 16 * m + (l & 15), c0 = 32 * cc + 8 * (l >> 4);
+    bf16x8 ph, pm, pl;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const float v = w[((long)co * C + c0 + u) * 27 + kd * 9 + k];
+      const __bf16 h = (__bf16)v;
+      const float r1 = v - (float)h;
+      const __bf16 mm = (__bf16)r1;
+      ph[u] = h;
+      pm[u] = mm;
+      pl[u] = (__bf16)(r1 - (float)mm);
+    }
+    const long o = (long)(e >> 6) * 3 * 64 + l;
+    out[o] = ph;
+    out[o + 64] = pm;
+    out[o + 128] = pl;
+  }
+}
+
+bool c3_channels(int c) { return c == 32 || c == 64 || c == 96 || c == 128; }
+
+}  // namespace
+
+extern "C" {
+
+int aanet_conv3d_supported(int c, int co, int kd, int kh, int kw, int stride, int pad, int dil,
+                           int groups) {
+  if (c <= 0 || co <= 0 || kd <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || dil <= 0 ||
+      groups <= 0)
+    return AANET_EINVAL;
+  const bool ok = kd == 3 && kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 &&
+                  groups == 1 && c3_channels(c) && c3_channels(co);
+  return ok ? AANET_OK : AANET_EUNSUPPORTED;
+}
+
+size_t aanet_conv3d_pack_bytes(int co, int c) {
+  if (!c3_channels(co) || !c3_channels(c)) return 0;
+  return (size_t)(co / 32) * (c / 32) * 27 * 2 * 3 * 1024;
+}
+
+int aanet_conv3d_pack_f32(const float *w, int co, int c, void *wsplit, aanet_stream_t stream) {
+  if (!w || !wsplit || !aanet_conv3d_pack_bytes(co, c)) return AANET_EINVAL;
+  const int total = (co / 32) * (c / 32) * 27 * 2 * 64;
+  hipLaunchKernelGGL(conv3d_pack_kernel, dim3(host_div_up(total, 256)), dim3(256), 0, as_hip(stream),
+                     w, reinterpret_cast<bf16x8 *>(wsplit), co, c);
+  return aanet_launch_status();
+}
+
+int aanet_conv3d_fused_f32(const float *x, const void *wsplit, const float *bias,
+                           const float *residual, int act, float *out, int n, int c, int d, int h,
+                           int w, int co, aanet_stream_t stream) {
+  if (!x || !wsplit || !out || n <= 0 || c <= 0 || d <= 0 || h <= 0 || w <= 0 || co <= 0 ||
+      act < 0 || act > 2)
+    return AANET_EINVAL;
+  if (!c3_channels(c) || !c3_channels(co)) return AANET_EINVAL;
+  // per-image buffer resources with 32-bit offsets
+  if ((long)d * h * w * c * 4 >= (1L << 31) || (long)d * h * w * co * 4 >= (1L << 31))
+    return AANET_EUNSUPPORTED;
+  const long tiles = (long)host_div_up(w, TC) * host_div_up(h, TR) * n;
+  if (tiles > 0x7fffffffL) return AANET_EUNSUPPORTED;
+  C3Args a;
+  a.x = x;
+  a.wsplit = reinterpret_cast<const bf16x8 *>(wsplit);
+  a.bias = bias;
+  a.res = residual;
+  a.out = out;
+  a.N = n, a.C = c, a.D = d, a.H = h, a.W = w, a.Co = co, a.act = act;
+  hipLaunchKernelGGL(conv3d_kernel, dim3((unsigned)tiles, co / 32), dim3(NT), 0, as_hip(stream), a);
+  return aanet_launch_status();
+}
+
+}  // extern "C"

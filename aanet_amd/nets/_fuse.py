@@ -40,7 +40,7 @@ def clear_fold_caches(module):
     writes through `.data` and HIP graph replays update a weight without bumping its _version."""
     for m in module.modules():
         for attr in ("_aanet_fold", "_aanet_fold_dense", "_aanet_affine", "_aanet_s2pack",
-                     "_aanet_s2pack_k", "_aanet_g3pack"):
+                     "_aanet_s2pack_k", "_aanet_g3pack", "_aanet_fold3d"):
             if attr in m.__dict__:
                 del m.__dict__[attr]
         for p in m.parameters(recurse=False):
@@ -84,6 +84,85 @@ def folded(conv, bn):
     conv._aanet_fold = (key, w, b, wp)
     _lib.note_cache_fill()
     return w, b, wp
+
+
+def folded3d(conv, bn):
+    """(bias, pre-split fragments) of a 3x3x3 Conv3d followed by eval BN (bn may be None) for
+    ops.conv3d_fused, cached on the conv module keyed by parameter versions like folded(); the
+    bias is None when neither the conv nor a BN has one."""
+    tensors = (conv.weight, conv.bias) + (_bn_tensors(bn) if bn is not None else ())
+    key = _key(*tensors)
+    cache = conv.__dict__.get("_aanet_fold3d")
+    if cache is not None and cache[0] == key:
+        return cache[1], cache[2]
+    with torch.no_grad():
+        if bn is None:
+            w = conv.weight
+            b = None if conv.bias is None else conv.bias.contiguous()
+        else:
+            scale, shift = bn_scale_shift(bn)
+            w = conv.weight * scale.view(-1, 1, 1, 1, 1)
+            b = (shift if conv.bias is None else conv.bias * scale + shift).contiguous()
+        wsplit = ops.pack_conv3d(w)
+    if wsplit is None:
+        raise ValueError("folded3d: a conv outside ops.conv3d_ok")
+    conv.__dict__["_aanet_fold3d"] = (key, b, wsplit)
+    _lib.note_cache_fill()
+    return b, wsplit
+
+
+def conv3d_bn_act(x, conv, bn=None, act=None, residual=None):
+    """act(BN(conv(x)) [+ residual]) of an ops.conv3d_ok Conv3d as ONE HIP kernel (BN folded into
+    the conv).  x and residual are channels_last_3d, and so is the result."""
+    b, wsplit = folded3d(conv, bn)
+    return ops.conv3d_fused(x, wsplit, b, conv.out_channels, act, residual)
+
+
+def to_ndhwc(x):
+    """x as a channels_last_3d tensor (a copy unless it already is one)."""
+    return x if _lib.is_ndhwc(x) else x.contiguous(memory_format=torch.channels_last_3d)
+
+
+# Whether the 3-D convs that stay on MIOpen (stride 2, transposed, one output channel) are handed
+# channels_last_3d tensors as they come out of the HIP kernel (True) or an NCDHW copy (False: the
+# layout they have always run on).  Measured on the PSMNet hourglass aggregator at the C5 volume
+# (B=8): 150 ms per forward as they come, 182 ms with the copies (22 layout copies, 41 ms;
+# profiles/c5_model_conv3d.txt, DESIGN.md 7).
+MIOPEN_NDHWC = True
+
+
+def to_ncdhw(x):
+    """x as an NCDHW-contiguous tensor (a copy unless it already is one)."""
+    return x.contiguous()
+
+
+def run_fused_chain3d(mods, x, residual=None):
+    """Run a flat module list of a 3-D aggregator in eval: each ops.conv3d_ok Conv3d
+    [+ BatchNorm3d] [+ ReLU | LeakyReLU(0.2)] run of it is ONE HIP kernel on channels_last_3d
+    tensors; anything else (stride-2 and transposed convs, one-channel heads) runs as is, on
+    MIOpen.  residual: added to the LAST conv's BN output when that conv ends the list with no
+    activation behind it (the `block(x) + x` adds of the aggregators)."""
+    i, n = 0, len(mods)
+    while i < n:
+        m = mods[i]
+        if ops.conv3d_ok(m):
+            bn = act = None
+            j = i + 1
+            if j < n and isinstance(mods[j], nn.BatchNorm3d):
+                bn, j = mods[j], j + 1
+            if j < n and act_name(mods[j]) not in (None, False):
+                act, j = act_name(mods[j]), j + 1
+            res = None
+            if residual is not None and j == n and act is None:
+                res, residual = to_ndhwc(residual), None
+            x = conv3d_bn_act(to_ndhwc(x), m, bn, act, res)
+            i = j
+        else:
+            if isinstance(m, (nn.Conv3d, nn.ConvTranspose3d)) and not MIOPEN_NDHWC:
+                x = to_ncdhw(x)
+            x = m(x)
+            i += 1
+    return x if residual is None else x + residual
 
 
 def deconv2x_ok(conv):

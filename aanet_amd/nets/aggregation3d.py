@@ -3,13 +3,29 @@
 
 Module trees follow the reference exactly -- including PSMNetBasicAggregation's reuse of ONE
 `conv1` block in several Sequentials (shared weights, aggregation.py:101-123), which a
-checkpoint load relies on.  The 3-D convs run on PyTorch (MIOpen); the volumes they consume
-come from the HIP concat / difference kernels (aanet_amd.nets.cost).
+checkpoint load relies on.  The volumes they consume come from the HIP concat / difference
+kernels (aanet_amd.nets.cost).
+
+In eval mode without autograd (nets/_fuse.py use_fused) every 3x3x3 stride-1 conv with 32..128
+input and output channels runs on the HIP kernel of csrc/conv3d.hip (ops.conv3d_fused) on
+channels_last_3d tensors, with its BatchNorm folded in and its activation -- and, where the graph
+has one, the residual add behind it -- in the epilogue.  The stride-2 and transposed convs and the
+one-channel heads run on PyTorch (MIOpen), as does everything in training, under autograd and with
+`aanet_fuse = False` (the reference op order, unchanged).
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 from .._precision import fp32_convs
+from .. import ops
+from . import _fuse
+from ._fuse import FoldCacheMixin, use_fused
+
+
+def _chain(seq, x, residual=None):
+    """The eval fast path of one Sequential (or bare module) of an aggregator."""
+    mods = list(_fuse._leaves(seq)) if isinstance(seq, nn.Sequential) else [seq]
+    return _fuse.run_fused_chain3d(mods, x, residual)
 
 
 def conv3d(in_channels, out_channels, kernel_size=3, stride=1, dilation=1, groups=1):
@@ -49,7 +65,7 @@ def _up4(cost):
                                        align_corners=False), 1)
 
 
-class StereoNetAggregation(nn.Module):
+class StereoNetAggregation(FoldCacheMixin, nn.Module):
     """aggregation.py:69-90: four conv3d blocks + a 1-channel Conv3d -> [B, D, H, W]."""
 
     def __init__(self, in_channels=32):
@@ -61,10 +77,13 @@ class StereoNetAggregation(nn.Module):
     @fp32_convs
     def forward(self, cost_volume):
         assert cost_volume.dim() == 5  # [B, C, D, H, W]
+        if use_fused(self, cost_volume):
+            y = _chain(self.aggregation_layer, cost_volume)
+            return _chain(self.final_conv, y).squeeze(1)
         return self.final_conv(self.aggregation_layer(cost_volume)).squeeze(1)
 
 
-class PSMNetBasicAggregation(nn.Module):
+class PSMNetBasicAggregation(FoldCacheMixin, nn.Module):
     """aggregation.py:93-138: 12 3-D convs (one shared conv1 block), x4 trilinear upsampling."""
 
     def __init__(self, max_disp):
@@ -81,13 +100,18 @@ class PSMNetBasicAggregation(nn.Module):
 
     @fp32_convs
     def forward(self, cost):
+        if use_fused(self, cost):
+            cost0 = _chain(self.dres0, cost)
+            for name in ("dres1", "dres2", "dres3", "dres4"):
+                cost0 = _chain(getattr(self, name), cost0, residual=cost0)
+            return [_up4(_chain(self.classify, cost0))]
         cost0 = self.dres0(cost)
         for name in ("dres1", "dres2", "dres3", "dres4"):
             cost0 = getattr(self, name)(cost0) + cost0
         return [_up4(self.classify(cost0))]
 
 
-class PSMNetHourglass(nn.Module):
+class PSMNetHourglass(FoldCacheMixin, nn.Module):
     """aggregation.py:142-189."""
 
     def __init__(self, inplanes):
@@ -108,7 +132,20 @@ class PSMNetHourglass(nn.Module):
                                    nn.BatchNorm3d(inplanes))
 
     @fp32_convs
-    def forward(self, x, presqu, postsqu):
+    def forward(self, x, presqu, postsqu, fused=None):
+        # fused: the enclosing aggregator's decision (None: this module's own, use_fused)
+        if use_fused(self, x) if fused is None else fused:
+            pre = _chain(self.conv1, x)
+            res = None if postsqu is None else _fuse.to_ndhwc(postsqu)
+            if ops.conv3d_ok(self.conv2[0]):  # relu(conv2(.) + postsqu) in one kernel
+                pre = _fuse.conv3d_bn_act(_fuse.to_ndhwc(pre), self.conv2[0], self.conv2[1], "relu", res)
+            else:
+                pre = self.conv2(_fuse.to_ncdhw(pre))
+                pre = F.relu(pre if postsqu is None else pre + postsqu, inplace=True)
+            out = _chain(self.conv4, _chain(self.conv3, pre))
+            post = _chain(self.conv5, out)
+            post = F.relu(post + (pre if presqu is None else presqu), inplace=True)
+            return _chain(self.conv6, post), pre, post
         pre = self.conv2(self.conv1(x))
         pre = F.relu(pre if postsqu is None else pre + postsqu, inplace=True)
         out = self.conv4(self.conv3(pre))
@@ -116,7 +153,7 @@ class PSMNetHourglass(nn.Module):
         return self.conv6(post), pre, post
 
 
-class PSMNetHGAggregation(nn.Module):
+class PSMNetHGAggregation(FoldCacheMixin, nn.Module):
     """aggregation.py:192-254: stacked hourglass; three cost outputs in training, one in eval."""
 
     def __init__(self, max_disp):
@@ -136,13 +173,15 @@ class PSMNetHGAggregation(nn.Module):
 
     @fp32_convs
     def forward(self, cost):
+        if use_fused(self, cost):
+            return self._forward_fused(cost)
         cost0 = self.dres0(cost)
         cost0 = self.dres1(cost0) + cost0
-        out1, pre1, post1 = self.dres2(cost0, None, None)
+        out1, pre1, post1 = self.dres2(cost0, None, None, fused=False)
         out1 = out1 + cost0
-        out2, _, post2 = self.dres3(out1, pre1, post1)
+        out2, _, post2 = self.dres3(out1, pre1, post1, fused=False)
         out2 = out2 + cost0
-        out3, _, _ = self.dres4(out2, pre1, post2)  # pre1, as the reference (not pre2)
+        out3, _, _ = self.dres4(out2, pre1, post2, fused=False)  # pre1, as the reference (not pre2)
         out3 = out3 + cost0
         cost1 = self.classif1(out1)
         cost2 = self.classif2(out2) + cost1
@@ -151,8 +190,28 @@ class PSMNetHGAggregation(nn.Module):
             return [_up4(cost1), _up4(cost2), _up4(cost3)]
         return [_up4(cost3)]
 
+    def _forward_fused(self, cost):
+        """Eval fast path: the same graph with the stride-1 convs on the HIP kernel.  The
+        hourglasses follow this module's decision.  When the MIOpen convs are given NCDHW copies
+        (_fuse.MIOPEN_NDHWC off) the hourglass outputs are NCDHW, and the `+ cost0` adds use an
+        NCDHW copy of cost0 so that their results are too."""
+        cost0 = _chain(self.dres0, cost)
+        cost0 = _chain(self.dres1, cost0, residual=cost0)
+        if not _fuse.MIOPEN_NDHWC:
+            cost0 = _fuse.to_ncdhw(cost0)
+        out1, pre1, post1 = self.dres2(cost0, None, None, fused=True)
+        out1 = out1 + cost0
+        out2, _, post2 = self.dres3(out1, pre1, post1, fused=True)
+        out2 = out2 + cost0
+        out3, _, _ = self.dres4(out2, pre1, post2, fused=True)  # pre1, as the reference (not pre2)
+        out3 = out3 + cost0
+        cost1 = _chain(self.classif1, out1)
+        cost2 = _chain(self.classif2, out2) + cost1
+        cost3 = _chain(self.classif3, out3) + cost2
+        return [_up4(cost3)]
 
-class GCNetAggregation(nn.Module):
+
+class GCNetAggregation(FoldCacheMixin, nn.Module):
     """aggregation.py:257-309: 3-D encoder-decoder down to 1/32 and back."""
 
     def __init__(self):
@@ -169,6 +228,17 @@ class GCNetAggregation(nn.Module):
 
     @fp32_convs
     def forward(self, cost_volume):
+        if use_fused(self, cost_volume):
+            skip1 = _chain(self.conv1, cost_volume)
+            a, skips = cost_volume, []
+            for lvl in (2, 3, 4, 5):
+                a = _chain(getattr(self, f"conv{lvl}a"), a)
+                skips.append(_chain(getattr(self, f"conv{lvl}b"), a))
+            x = _chain(self.trans_conv1, skips[3])
+            x = _chain(self.trans_conv2, x + skips[2])
+            x = _chain(self.trans_conv3, x + skips[1])
+            x = _chain(self.trans_conv4, x + skips[0])
+            return torch.squeeze(_chain(self.trans_conv5, x + skip1), 1)
         skip1 = self.conv1(cost_volume)
         a, skips = cost_volume, []
         for lvl in (2, 3, 4, 5):

@@ -707,6 +707,90 @@ def conv3x3_grouped_nhwc(x, wsplit, bias, co, groups, dilation):
     return out
 
 
+# ------------------------------------------------------- 3-D aggregator convs (conv3d.hip) ------
+# Shapes that aanet_conv3d_supported takes but that lost to MIOpen in tools/conv3d_bench.py on the
+# MI355X: (c, co) pairs conv3d_ok refuses so they stay on MIOpen (DESIGN.md 7 names each).
+CONV3D_SLOWER_THAN_MIOPEN = frozenset()
+
+
+def conv3d_supported(c, co, kernel=3, stride=1, padding=1, dilation=1, groups=1):
+    """Whether aanet_conv3d_fused_f32 takes a Conv3d of these parameters
+    (aanet_conv3d_supported): 3x3x3, stride 1, padding 1, dilation 1, one group, c and co in
+    {32, 64, 96, 128}."""
+    kd, kh, kw = (kernel,) * 3 if isinstance(kernel, int) else kernel
+    return _lib.lib().aanet_conv3d_supported(c, co, kd, kh, kw, stride, padding, dilation,
+                                             groups) == 0
+
+
+def conv3d_ok(conv):
+    """A conv module that conv3d_fused runs (aanet_conv3d_supported and the measured dispatch
+    table): nn.Conv3d or a subclass, zero padding, cubic parameters."""
+    if not isinstance(conv, torch.nn.Conv3d) or conv.padding_mode != "zeros" or \
+            isinstance(conv.padding, str):
+        return False
+    vals = []
+    for v in (conv.stride, conv.padding, conv.dilation):
+        if len(set(v)) != 1:
+            return False
+        vals.append(v[0])
+    c, co = conv.in_channels, conv.out_channels
+    return conv3d_supported(c, co, tuple(conv.kernel_size), *vals, conv.groups) and \
+        (c, co) not in CONV3D_SLOWER_THAN_MIOPEN
+
+
+def pack_conv3d(weight):
+    """Pre-split A fragments of a [co][c][3][3][3] weight for conv3d_fused (aanet_conv3d_pack_f32),
+    or None when the shape is outside the kernel."""
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
+        return None
+    if not weight.is_cuda:
+        raise NotImplementedError(
+            f"aanet_amd ops run only on the MI355X (HIP) device; weight is on {weight.device}")
+    co, c = weight.shape[:2]
+    nbytes = _lib.lib().aanet_conv3d_pack_bytes(co, c)
+    if not nbytes:
+        return None
+    out = torch.empty(nbytes // 2, device=weight.device, dtype=torch.int16)
+    w = weight.contiguous().float()
+    call("aanet_conv3d_pack_f32", ptr(w), co, c, ptr(out), stream_of(w))
+    return out
+
+
+def conv3d_fused(x, wsplit, bias, co, act=None, residual=None, out=None):
+    """act(conv3d(x, W) + bias [+ residual]) for a 3x3x3 stride-1 pad-1 conv with BN folded into
+    W / bias (aanet_conv3d_fused_f32; wsplit = pack_conv3d(W)).  x [N, C, D, H, W] and residual
+    [N, co, D, H, W] are channels_last_3d; so is the result (the caller's `out` when given)."""
+    for nm, t in (("x", x), ("wsplit", wsplit), ("bias", bias), ("residual", residual), ("out", out)):
+        if t is not None and not t.is_cuda:
+            raise NotImplementedError(
+                f"aanet_amd ops run only on the MI355X (HIP) device; {nm} is on {t.device}")
+    if x.dim() != 5:
+        raise ValueError("conv3d_fused: x must be [N, C, D, H, W]")
+    N, C, D, H, W = x.shape
+    shape = (N, co, D, H, W)
+    for nm, t, shp in (("x", x, tuple(x.shape)), ("residual", residual, shape), ("out", out, shape)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or tuple(t.shape) != shp or not _lib.is_ndhwc(t) or \
+                t.device != x.device:
+            raise ValueError(f"conv3d_fused: {nm} must be a channels_last_3d float32 tensor of "
+                             f"shape {shp} on {x.device}")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (co,) or
+                             not bias.is_contiguous()):
+        raise ValueError(f"conv3d_fused: bias must be a contiguous float32 tensor of shape ({co},)")
+    nbytes = _lib.lib().aanet_conv3d_pack_bytes(co, C)
+    if not nbytes or wsplit.numel() * wsplit.element_size() != nbytes:
+        raise ValueError(f"conv3d_fused: wsplit is not pack_conv3d of a [{co}][{C}][3][3][3] weight")
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=x.dtype,
+                          memory_format=torch.channels_last_3d)
+    if x.numel() == 0:
+        return out
+    call("aanet_conv3d_fused_f32", ptr(x), ptr(wsplit), ptr(bias), ptr(residual), ACT[act],
+         ptr(out), N, C, D, H, W, co, stream_of(x))
+    return out
+
+
 def csa_sum(inputs, act="leaky"):
     """act(inputs[0] + resize(inputs[1]) + ...) at inputs[0]'s size (aggregation.py:387-400)."""
     require_gpu(*inputs)

@@ -361,6 +361,30 @@ int aanet_conv3x3_grouped_nhwc_f32(const float *x, const void *wsplit, const flo
                                    int c, int h, int w, int co, int groups, int dil, float *out,
                                    aanet_stream_t stream);
 
+/* The 3-D aggregators' convs in eval (nets/aggregation.py:8-21,52-67: nn.Conv3d(c, co, 3,
+ * stride 1, padding 1, bias=False) + BatchNorm3d [+ ReLU | LeakyReLU(0.2)], BN folded into
+ * weight / bias by the caller), with the residual add that follows some of them:
+ *   out = act(conv3d(x, W) + bias [+ residual]),  act: 0 none, 1 ReLU, 2 LeakyReLU(0.2).
+ * x [n][d][h][w][c], residual and out [n][d][h][w][co]: channels-last (torch channels_last_3d);
+ * bias [co] and residual may be NULL.  c, co in {32, 64, 96, 128} (AANET_EINVAL otherwise);
+ * AANET_EUNSUPPORTED when one image's input or output volume reaches 2^31 bytes (per-image
+ * buffer resources with 32-bit offsets).  wsplit: aanet_conv3d_pack_f32 of the
+ * [co][c][3][3][3] weight into aanet_conv3d_pack_bytes(co, c) device bytes (0: channel counts
+ * outside the kernel) -- round-to-nearest bf16 piece fragments in the kernel's A-operand order.
+ * Split-bf16 contraction (fp32-accurate, see AANET_CONV_EXACT_F32 above for the arithmetic);
+ * the result of an image does not depend on the batch it is in. */
+size_t aanet_conv3d_pack_bytes(int co, int c);
+int aanet_conv3d_pack_f32(const float *w, int co, int c, void *wsplit, aanet_stream_t stream);
+int aanet_conv3d_fused_f32(const float *x, const void *wsplit, const float *bias,
+                           const float *residual, int act, float *out, int n, int c, int d, int h,
+                           int w, int co, aanet_stream_t stream);
+/* Host-only: AANET_OK when aanet_conv3d_fused_f32 takes a Conv3d of these parameters
+ * (nets/aggregation.py:8-21,52-67: 3x3x3, stride 1, padding 1, dilation 1, one group, c and co
+ * in {32, 64, 96, 128}), AANET_EUNSUPPORTED for any other conv, AANET_EINVAL for a parameter
+ * that is not positive (pad: negative).  Touches no device. */
+int aanet_conv3d_supported(int c, int co, int kd, int kh, int kw, int stride, int pad, int dil,
+                           int groups);
+
 /* aanet_conv3x3s2_f32 with the CSA sum of output a in its epilogue (aggregation.py:388-400 for an
  * output branch whose finer-scale term is this conv):
  *   out_a = act_a(conv + bias [+ identity] [+ resize(up)])
