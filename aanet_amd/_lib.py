@@ -61,6 +61,12 @@ _SIGNATURES = {
     "aanet_conv3d_pack_f32": [_P, _I, _I, _P, _P],
     "aanet_conv3d_fused_f32": [_P, _P, _P, _P, _I, _P] + [_I] * 6 + [_P],
     "aanet_conv3d_supported": [_I] * 9,
+    "aanet_conv3d_s2_pack_f32": [_P, _I, _I, _P, _P],
+    "aanet_conv3d_s2_fused_f32": [_P, _P, _P, _P, _I, _P] + [_I] * 6 + [_P],
+    "aanet_conv3d_s2_supported": [_I] * 9,
+    "aanet_deconv3d2x_pack_f32": [_P, _I, _I, _P, _P],
+    "aanet_deconv3d2x_fused_f32": [_P, _P, _P, _P, _I, _P] + [_I] * 6 + [_P],
+    "aanet_deconv3d2x_supported": [_I] * 10,
     "aanet_mdcn_im2col_f32": [_P, _P, _P, _P] + [_I] * 9 + [_P],
     "aanet_mdcn_sample_index": [_P, _P, _P, _P] + [_I] * 9 + [_P],
     "aanet_conv_engine_plan": [_P, _P],
@@ -77,6 +83,8 @@ _SIZE_FUNCTIONS = [
     ("aanet_conv3x3_grouped_pack_bytes", [_I, _I, _I], ctypes.c_size_t),
     ("aanet_mdcn_window_fwd_supported", [_I] * 10, _I),
     ("aanet_conv3d_pack_bytes", [_I, _I], ctypes.c_size_t),
+    ("aanet_conv3d_s2_pack_bytes", [_I, _I], ctypes.c_size_t),
+    ("aanet_deconv3d2x_pack_bytes", [_I, _I], ctypes.c_size_t),
 ]
 
 _lib = None

@@ -26,8 +26,7 @@
 // output the order is input plane, chunk, in-plane tap ascending -- independent of the batch.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
-#include "split.h"
+#include "conv3d_common.h"
 
 namespace {
 
@@ -37,7 +36,7 @@ constexpr int HWW = TC + 2, HR = TR + 2;    // halo
 constexpr int NPOS = HR * HWW;              // 180 positions
 constexpr int PE = NPOS * 32;               // bf16 per piece plane
 constexpr int HIT = (NPOS * 4 + NT - 1) / NT;  // halo octets (8 channels of a position) per thread
-constexpr unsigned OOB = 0x80000000u;
+constexpr unsigned OOB = C3_OOB;
 
 struct C3Args {
   const float *x;      // [N][D][H][W][C]
@@ -47,11 +46,6 @@ struct C3Args {
   float *out;          // [N][D][H][W][Co]
   int N, C, D, H, W, Co, act;
 };
-
-// bf16 offset of 16-byte slot q8 (channels 8 q8 .. 8 q8 + 7) of halo position pos (conv_g3.hip)
-__device__ __forceinline__ int c3_swz(int pos, int q8) {
-  return pos * 32 + ((q8 ^ (((pos >> 2) & 1) << 1)) << 3);
-}
 
 __global__ __launch_bounds__(NT, 2) void conv3d_kernel(C3Args a) {
   __shared__ __attribute__((aligned(16))) __bf16 sH[3 * PE];
@@ -190,40 +184,6 @@ __global__ __launch_bounds__(NT, 2) void conv3d_kernel(C3Args a) {
   store_plane(D - 1, acc[0]);
 }
 
-// w [Co][C][3][3][3] fp32 -> [Co/32][C/32][9 (kh,kw)][3 kd][2][3 pieces][64 lanes][8 bf16]: lane l
-// of co block m holds row 32cb + 16m + l%16, channels 32cc + 8(l/16) + 0..7, as three bf16 pieces
-// (round to nearest: h = bf16(x), m = bf16(x - h), l = bf16(x - h - m))
-__global__ void conv3d_pack_kernel(const float *__restrict__ w, bf16x8 *__restrict__ out, int Co, int C) {
-  const int ncc = C / 32, total = (Co / 32) * ncc * 27 * 2 * 64;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    const int l = e & 63, m = (e >> 6) & 1;
-    int r = e >> 7;
-    const int kd = r % 3;
-    r /= 3;
-    const int k = r % 9;
-    r /= 9;
-    const int cc = r % ncc, cb = r / ncc;
-    const int co = 32 * cb + 16 * m + (l & 15), c0 = 32 * cc + 8 * (l >> 4);
-    bf16x8 ph, pm, pl;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const float v = w[((long)co * C + c0 + u) * 27 + kd * 9 + k];
-      const __bf16 h = (__bf16)v;
-      const float r1 = v - (float)h;
-      const __bf16 mm = (__bf16)r1;
-      ph[u] = h;
-      pm[u] = mm;
-      pl[u] = (__bf16)(r1 - (float)mm);
-    }
-    const long o = (long)(e >> 6) * 3 * 64 + l;
-    out[o] = ph;
-    out[o + 64] = pm;
-    out[o + 128] = pl;
-  }
-}
-
-bool c3_channels(int c) { return c == 32 || c == 64 || c == 96 || c == 128; }
-
 }  // namespace
 
 extern "C" {
@@ -238,17 +198,10 @@ int aanet_conv3d_supported(int c, int co, int kd, int kh, int kw, int stride, in
   return ok ? AANET_OK : AANET_EUNSUPPORTED;
 }
 
-size_t aanet_conv3d_pack_bytes(int co, int c) {
-  if (!c3_channels(co) || !c3_channels(c)) return 0;
-  return (size_t)(co / 32) * (c / 32) * 27 * 2 * 3 * 1024;
-}
+size_t aanet_conv3d_pack_bytes(int co, int c) { return c3_pack_bytes(co, c); }
 
 int aanet_conv3d_pack_f32(const float *w, int co, int c, void *wsplit, aanet_stream_t stream) {
-  if (!w || !wsplit || !aanet_conv3d_pack_bytes(co, c)) return AANET_EINVAL;
-  const int total = (co / 32) * (c / 32) * 27 * 2 * 64;
-  hipLaunchKernelGGL(conv3d_pack_kernel, dim3(host_div_up(total, 256)), dim3(256), 0, as_hip(stream),
-                     w, reinterpret_cast<bf16x8 *>(wsplit), co, c);
-  return aanet_launch_status();
+  return c3_pack<false>(w, co, c, wsplit, stream);
 }
 
 int aanet_conv3d_fused_f32(const float *x, const void *wsplit, const float *bias,

@@ -40,7 +40,8 @@ def clear_fold_caches(module):
     writes through `.data` and HIP graph replays update a weight without bumping its _version."""
     for m in module.modules():
         for attr in ("_aanet_fold", "_aanet_fold_dense", "_aanet_affine", "_aanet_s2pack",
-                     "_aanet_s2pack_k", "_aanet_g3pack", "_aanet_fold3d"):
+                     "_aanet_s2pack_k", "_aanet_g3pack", "_aanet_fold3d", "_aanet_fold3d_s2",
+                     "_aanet_fold3d_up"):
             if attr in m.__dict__:
                 del m.__dict__[attr]
         for p in m.parameters(recurse=False):
@@ -118,12 +119,47 @@ def conv3d_bn_act(x, conv, bn=None, act=None, residual=None):
     return ops.conv3d_fused(x, wsplit, b, conv.out_channels, act, residual)
 
 
+def folded3d_resample(conv, bn):
+    """folded3d for an ops.conv3d_s2_ok Conv3d (ops.conv3d_s2_fused) or an ops.deconv3d2x_ok
+    ConvTranspose3d (ops.deconv3d2x_fused), whose weight has its output channels in dimension 1."""
+    up = isinstance(conv, nn.ConvTranspose3d)
+    attr = "_aanet_fold3d_up" if up else "_aanet_fold3d_s2"
+    tensors = (conv.weight, conv.bias) + (_bn_tensors(bn) if bn is not None else ())
+    key = _key(*tensors)
+    cache = conv.__dict__.get(attr)
+    if cache is not None and cache[0] == key:
+        return cache[1], cache[2]
+    with torch.no_grad():
+        if bn is None:
+            w = conv.weight
+            b = None if conv.bias is None else conv.bias.contiguous()
+        else:
+            scale, shift = bn_scale_shift(bn)
+            w = conv.weight * (scale.view(1, -1, 1, 1, 1) if up else scale.view(-1, 1, 1, 1, 1))
+            b = (shift if conv.bias is None else conv.bias * scale + shift).contiguous()
+        wsplit = ops.pack_deconv3d2x(w) if up else ops.pack_conv3d_s2(w)
+    if wsplit is None:
+        raise ValueError("folded3d_resample: a conv outside ops.conv3d_s2_ok / ops.deconv3d2x_ok")
+    conv.__dict__[attr] = (key, b, wsplit)
+    _lib.note_cache_fill()
+    return b, wsplit
+
+
+def resample3d_bn_act(x, conv, bn=None, act=None, residual=None):
+    """conv3d_bn_act for an ops.conv3d_s2_ok Conv3d or an ops.deconv3d2x_ok ConvTranspose3d:
+    act(BN(conv(x)) [+ residual]) as ONE HIP kernel on channels_last_3d tensors."""
+    b, wsplit = folded3d_resample(conv, bn)
+    fn = ops.deconv3d2x_fused if isinstance(conv, nn.ConvTranspose3d) else ops.conv3d_s2_fused
+    return fn(x, wsplit, b, conv.out_channels, act, residual)
+
+
 def to_ndhwc(x):
     """x as a channels_last_3d tensor (a copy unless it already is one)."""
     return x if _lib.is_ndhwc(x) else x.contiguous(memory_format=torch.channels_last_3d)
 
 
-# Whether the 3-D convs that stay on MIOpen (stride 2, transposed, one output channel) are handed
+# Whether the 3-D convs that stay on MIOpen (one output channel, GC-Net's last transposed conv, and
+# any shape in a SLOWER_THAN_MIOPEN set of ops) are handed
 # channels_last_3d tensors as they come out of the HIP kernel (True) or an NCDHW copy (False: the
 # layout they have always run on).  Measured on the PSMNet hourglass aggregator at the C5 volume
 # (B=8): 150 ms per forward as they come, 182 ms with the copies (22 layout copies, 41 ms;
@@ -137,15 +173,17 @@ def to_ncdhw(x):
 
 
 def run_fused_chain3d(mods, x, residual=None):
-    """Run a flat module list of a 3-D aggregator in eval: each ops.conv3d_ok Conv3d
-    [+ BatchNorm3d] [+ ReLU | LeakyReLU(0.2)] run of it is ONE HIP kernel on channels_last_3d
-    tensors; anything else (stride-2 and transposed convs, one-channel heads) runs as is, on
-    MIOpen.  residual: added to the LAST conv's BN output when that conv ends the list with no
-    activation behind it (the `block(x) + x` adds of the aggregators)."""
+    """Run a flat module list of a 3-D aggregator in eval: each ops.conv3d_ok (stride 1) or
+    ops.conv3d_s2_ok (stride 2) Conv3d or ops.deconv3d2x_ok ConvTranspose3d [+ BatchNorm3d]
+    [+ ReLU | LeakyReLU(0.2)] run of it is ONE HIP kernel on channels_last_3d tensors; anything
+    else (one-channel heads, a transposed conv without output padding) runs as is, on MIOpen.
+    residual: added to the LAST conv's BN output when that conv ends the list with no activation
+    behind it (the `block(x) + x` adds of the aggregators)."""
     i, n = 0, len(mods)
     while i < n:
         m = mods[i]
-        if ops.conv3d_ok(m):
+        s1 = ops.conv3d_ok(m)
+        if s1 or ops.conv3d_s2_ok(m) or ops.deconv3d2x_ok(m):
             bn = act = None
             j = i + 1
             if j < n and isinstance(mods[j], nn.BatchNorm3d):
@@ -155,7 +193,7 @@ def run_fused_chain3d(mods, x, residual=None):
             res = None
             if residual is not None and j == n and act is None:
                 res, residual = to_ndhwc(residual), None
-            x = conv3d_bn_act(to_ndhwc(x), m, bn, act, res)
+            x = (conv3d_bn_act if s1 else resample3d_bn_act)(to_ndhwc(x), m, bn, act, res)
             i = j
         else:
             if isinstance(m, (nn.Conv3d, nn.ConvTranspose3d)) and not MIOPEN_NDHWC:

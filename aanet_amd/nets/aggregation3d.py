@@ -6,12 +6,16 @@ Module trees follow the reference exactly -- including PSMNetBasicAggregation's 
 checkpoint load relies on.  The volumes they consume come from the HIP concat / difference
 kernels (aanet_amd.nets.cost).
 
-In eval mode without autograd (nets/_fuse.py use_fused) every 3x3x3 stride-1 conv with 32..128
-input and output channels runs on the HIP kernel of csrc/conv3d.hip (ops.conv3d_fused) on
-channels_last_3d tensors, with its BatchNorm folded in and its activation -- and, where the graph
-has one, the residual add behind it -- in the epilogue.  The stride-2 and transposed convs and the
-one-channel heads run on PyTorch (MIOpen), as does everything in training, under autograd and with
-`aanet_fuse = False` (the reference op order, unchanged).
+In eval mode without autograd (nets/_fuse.py use_fused) every 3x3x3 conv with 32..128 input and
+output channels runs on a HIP kernel on channels_last_3d tensors, with its BatchNorm folded in and
+its activation -- and, where the graph has one, the residual add behind it -- in the epilogue:
+the stride-1 convs on csrc/conv3d.hip (ops.conv3d_fused), the stride-2 convs on csrc/conv3d_s2.hip
+(ops.conv3d_s2_fused) and the stride-2 transposed convs with output padding 1 on
+csrc/deconv3d.hip (ops.deconv3d2x_fused).  In the PSMNet hourglass conv5's `relu(. + pre)` and
+conv6's `+ cost0` of the enclosing aggregator are residuals of those launches; GC-Net's
+`x + skip` adds follow a ReLU and stay torch adds.  The one-channel heads and GC-Net's
+trans_conv5 (32 -> 1, no output padding) run on PyTorch (MIOpen), as does everything in training,
+under autograd and with `aanet_fuse = False` (the reference op order, unchanged).
 """
 import torch
 import torch.nn as nn
@@ -132,8 +136,10 @@ class PSMNetHourglass(FoldCacheMixin, nn.Module):
                                    nn.BatchNorm3d(inplanes))
 
     @fp32_convs
-    def forward(self, x, presqu, postsqu, fused=None):
-        # fused: the enclosing aggregator's decision (None: this module's own, use_fused)
+    def forward(self, x, presqu, postsqu, fused=None, out_residual=None):
+        # fused: the enclosing aggregator's decision (None: this module's own, use_fused).
+        # out_residual: a tensor to add to the first result (the aggregator's `+ cost0`), which
+        # on the fused path goes into conv6's launch
         if use_fused(self, x) if fused is None else fused:
             pre = _chain(self.conv1, x)
             res = None if postsqu is None else _fuse.to_ndhwc(postsqu)
@@ -143,14 +149,19 @@ class PSMNetHourglass(FoldCacheMixin, nn.Module):
                 pre = self.conv2(_fuse.to_ncdhw(pre))
                 pre = F.relu(pre if postsqu is None else pre + postsqu, inplace=True)
             out = _chain(self.conv4, _chain(self.conv3, pre))
-            post = _chain(self.conv5, out)
-            post = F.relu(post + (pre if presqu is None else presqu), inplace=True)
-            return _chain(self.conv6, post), pre, post
+            skip = pre if presqu is None else presqu
+            if ops.deconv3d2x_ok(self.conv5[0]):  # relu(conv5(.) + skip) in one kernel
+                post = _fuse.resample3d_bn_act(_fuse.to_ndhwc(out), self.conv5[0], self.conv5[1],
+                                               "relu", _fuse.to_ndhwc(skip))
+            else:
+                post = F.relu(_chain(self.conv5, out) + skip, inplace=True)
+            return _chain(self.conv6, post, residual=out_residual), pre, post
         pre = self.conv2(self.conv1(x))
         pre = F.relu(pre if postsqu is None else pre + postsqu, inplace=True)
         out = self.conv4(self.conv3(pre))
         post = F.relu(self.conv5(out) + (pre if presqu is None else presqu), inplace=True)
-        return self.conv6(post), pre, post
+        out = self.conv6(post)
+        return out if out_residual is None else out + out_residual, pre, post
 
 
 class PSMNetHGAggregation(FoldCacheMixin, nn.Module):
@@ -191,7 +202,8 @@ class PSMNetHGAggregation(FoldCacheMixin, nn.Module):
         return [_up4(cost3)]
 
     def _forward_fused(self, cost):
-        """Eval fast path: the same graph with the stride-1 convs on the HIP kernel.  The
+        """Eval fast path: the same graph with the multi-channel convs on the HIP kernels; the
+        `+ cost0` adds are conv6's residual (a torch add where conv6 stays on MIOpen).  The
         hourglasses follow this module's decision.  When the MIOpen convs are given NCDHW copies
         (_fuse.MIOPEN_NDHWC off) the hourglass outputs are NCDHW, and the `+ cost0` adds use an
         NCDHW copy of cost0 so that their results are too."""
@@ -199,12 +211,10 @@ class PSMNetHGAggregation(FoldCacheMixin, nn.Module):
         cost0 = _chain(self.dres1, cost0, residual=cost0)
         if not _fuse.MIOPEN_NDHWC:
             cost0 = _fuse.to_ncdhw(cost0)
-        out1, pre1, post1 = self.dres2(cost0, None, None, fused=True)
-        out1 = out1 + cost0
-        out2, _, post2 = self.dres3(out1, pre1, post1, fused=True)
-        out2 = out2 + cost0
-        out3, _, _ = self.dres4(out2, pre1, post2, fused=True)  # pre1, as the reference (not pre2)
-        out3 = out3 + cost0
+        out1, pre1, post1 = self.dres2(cost0, None, None, fused=True, out_residual=cost0)
+        out2, _, post2 = self.dres3(out1, pre1, post1, fused=True, out_residual=cost0)
+        # pre1, as the reference (not pre2)
+        out3, _, _ = self.dres4(out2, pre1, post2, fused=True, out_residual=cost0)
         cost1 = _chain(self.classif1, out1)
         cost2 = _chain(self.classif2, out2) + cost1
         cost3 = _chain(self.classif3, out3) + cost2

@@ -791,6 +791,149 @@ def conv3d_fused(x, wsplit, bias, co, act=None, residual=None, out=None):
     return out
 
 
+# ------------------------- the hourglasses' down- / up-sampling convs (conv3d_s2.hip, deconv3d.hip)
+# (c, co) pairs the kernels take but that lost to MIOpen in tools/conv3d_bench.py on the MI355X;
+# conv3d_s2_ok / deconv3d2x_ok refuse them so they stay on MIOpen (DESIGN.md 7 names each).
+CONV3D_S2_SLOWER_THAN_MIOPEN = frozenset()
+DECONV3D2X_SLOWER_THAN_MIOPEN = frozenset()
+
+
+def conv3d_s2_supported(c, co, kernel=3, stride=2, padding=1, dilation=1, groups=1):
+    """Whether aanet_conv3d_s2_fused_f32 takes a Conv3d of these parameters
+    (aanet_conv3d_s2_supported): 3x3x3, stride 2, padding 1, dilation 1, one group, c and co in
+    {32, 64, 96, 128}."""
+    kd, kh, kw = (kernel,) * 3 if isinstance(kernel, int) else kernel
+    return _lib.lib().aanet_conv3d_s2_supported(c, co, kd, kh, kw, stride, padding, dilation,
+                                                groups) == 0
+
+
+def deconv3d2x_supported(c, co, kernel=3, stride=2, padding=1, output_padding=1, dilation=1,
+                         groups=1):
+    """Whether aanet_deconv3d2x_fused_f32 takes a ConvTranspose3d of these parameters
+    (aanet_deconv3d2x_supported): 3x3x3, stride 2, padding 1, output padding 1, dilation 1, one
+    group, c and co in {32, 64, 96, 128}."""
+    kd, kh, kw = (kernel,) * 3 if isinstance(kernel, int) else kernel
+    return _lib.lib().aanet_deconv3d2x_supported(c, co, kd, kh, kw, stride, padding,
+                                                 output_padding, dilation, groups) == 0
+
+
+def _cubic(conv, names):
+    """The common value of each of conv's per-axis parameters, or None when one is not cubic."""
+    vals = []
+    for nm in names:
+        v = getattr(conv, nm)
+        if len(set(v)) != 1:
+            return None
+        vals.append(v[0])
+    return vals
+
+
+def conv3d_s2_ok(conv):
+    """A conv module that conv3d_s2_fused runs (aanet_conv3d_s2_supported and the measured
+    dispatch table): nn.Conv3d or a subclass, zero padding, cubic parameters."""
+    if not isinstance(conv, torch.nn.Conv3d) or conv.padding_mode != "zeros" or \
+            isinstance(conv.padding, str):
+        return False
+    vals = _cubic(conv, ("stride", "padding", "dilation"))
+    c, co = conv.in_channels, conv.out_channels
+    return vals is not None and \
+        conv3d_s2_supported(c, co, tuple(conv.kernel_size), *vals, conv.groups) and \
+        (c, co) not in CONV3D_S2_SLOWER_THAN_MIOPEN
+
+
+def deconv3d2x_ok(conv):
+    """A transposed conv module that deconv3d2x_fused runs (aanet_deconv3d2x_supported and the
+    measured dispatch table): nn.ConvTranspose3d or a subclass, cubic parameters."""
+    if not isinstance(conv, torch.nn.ConvTranspose3d) or conv.padding_mode != "zeros":
+        return False
+    vals = _cubic(conv, ("stride", "padding", "output_padding", "dilation"))
+    c, co = conv.in_channels, conv.out_channels
+    return vals is not None and \
+        deconv3d2x_supported(c, co, tuple(conv.kernel_size), *vals, conv.groups) and \
+        (c, co) not in DECONV3D2X_SLOWER_THAN_MIOPEN
+
+
+def _pack3d(stem, weight, co, c):
+    if not weight.is_cuda:
+        raise NotImplementedError(
+            f"aanet_amd ops run only on the MI355X (HIP) device; weight is on {weight.device}")
+    nbytes = getattr(_lib.lib(), f"aanet_{stem}_pack_bytes")(co, c)
+    if not nbytes:
+        return None
+    out = torch.empty(nbytes // 2, device=weight.device, dtype=torch.int16)
+    w = weight.contiguous().float()
+    call(f"aanet_{stem}_pack_f32", ptr(w), co, c, ptr(out), stream_of(w))
+    return out
+
+
+def pack_conv3d_s2(weight):
+    """Pre-split A fragments of a [co][c][3][3][3] Conv3d weight for conv3d_s2_fused
+    (aanet_conv3d_s2_pack_f32), or None when the shape is outside the kernel."""
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
+        return None
+    return _pack3d("conv3d_s2", weight, weight.shape[0], weight.shape[1])
+
+
+def pack_deconv3d2x(weight):
+    """Pre-split A fragments of a [c][co][3][3][3] ConvTranspose3d weight for deconv3d2x_fused
+    (aanet_deconv3d2x_pack_f32), or None when the shape is outside the kernel."""
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
+        return None
+    return _pack3d("deconv3d2x", weight, weight.shape[1], weight.shape[0])
+
+
+def _resample3d_fused(name, stem, packer, osize, x, wsplit, bias, co, act, residual, out):
+    """conv3d_fused's checks and launch for a kernel whose output is osize(d, h, w)."""
+    for nm, t in (("x", x), ("wsplit", wsplit), ("bias", bias), ("residual", residual), ("out", out)):
+        if t is not None and not t.is_cuda:
+            raise NotImplementedError(
+                f"aanet_amd ops run only on the MI355X (HIP) device; {nm} is on {t.device}")
+    if x.dim() != 5:
+        raise ValueError(f"{name}: x must be [N, C, D, H, W]")
+    N, C, D, H, W = x.shape
+    shape = (N, co) + tuple(osize(v) for v in (D, H, W))
+    for nm, t, shp in (("x", x, tuple(x.shape)), ("residual", residual, shape), ("out", out, shape)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or tuple(t.shape) != shp or not _lib.is_ndhwc(t) or \
+                t.device != x.device:
+            raise ValueError(f"{name}: {nm} must be a channels_last_3d float32 tensor of "
+                             f"shape {shp} on {x.device}")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (co,) or
+                             not bias.is_contiguous()):
+        raise ValueError(f"{name}: bias must be a contiguous float32 tensor of shape ({co},)")
+    nbytes = getattr(_lib.lib(), f"aanet_{stem}_pack_bytes")(co, C)
+    if not nbytes or wsplit.numel() * wsplit.element_size() != nbytes:
+        raise ValueError(f"{name}: wsplit is not {packer} of a 3x3x3 weight with {C} input and "
+                         f"{co} output channels")
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=x.dtype,
+                          memory_format=torch.channels_last_3d)
+    if x.numel() == 0:
+        return out
+    call(f"aanet_{stem}_fused_f32", ptr(x), ptr(wsplit), ptr(bias), ptr(residual), ACT[act],
+         ptr(out), N, C, D, H, W, co, stream_of(x))
+    return out
+
+
+def conv3d_s2_fused(x, wsplit, bias, co, act=None, residual=None, out=None):
+    """act(conv3d(x, W, stride 2, padding 1) + bias [+ residual]) for a 3x3x3 conv with BN folded
+    into W / bias (aanet_conv3d_s2_fused_f32; wsplit = pack_conv3d_s2(W)).  x [N, C, D, H, W] and
+    residual [N, co, (D+1)//2, (H+1)//2, (W+1)//2] are channels_last_3d; so is the result (the
+    caller's `out` when given)."""
+    return _resample3d_fused("conv3d_s2_fused", "conv3d_s2", "pack_conv3d_s2",
+                             lambda v: (v + 1) // 2, x, wsplit, bias, co, act, residual, out)
+
+
+def deconv3d2x_fused(x, wsplit, bias, co, act=None, residual=None, out=None):
+    """act(conv_transpose3d(x, W, stride 2, padding 1, output_padding 1) + bias [+ residual]) for
+    a 3x3x3 transposed conv with BN folded into W / bias (aanet_deconv3d2x_fused_f32; wsplit =
+    pack_deconv3d2x(W)).  x [N, C, D, H, W] and residual [N, co, 2D, 2H, 2W] are
+    channels_last_3d; so is the result (the caller's `out` when given)."""
+    return _resample3d_fused("deconv3d2x_fused", "deconv3d2x", "pack_deconv3d2x",
+                             lambda v: 2 * v, x, wsplit, bias, co, act, residual, out)
+
+
 def csa_sum(inputs, act="leaky"):
     """act(inputs[0] + resize(inputs[1]) + ...) at inputs[0]'s size (aggregation.py:387-400)."""
     require_gpu(*inputs)

@@ -385,6 +385,45 @@ int aanet_conv3d_fused_f32(const float *x, const void *wsplit, const float *bias
 int aanet_conv3d_supported(int c, int co, int kd, int kh, int kw, int stride, int pad, int dil,
                            int groups);
 
+/* The 3-D aggregators' down-sampling convs in eval (nets/aggregation.py:142-189, 257-309:
+ * nn.Conv3d(c, co, 3, stride 2, padding 1, bias=False) + BatchNorm3d [+ ReLU], BN folded by the
+ * caller):
+ *   out = act(conv3d(x, W, stride 2, padding 1) + bias [+ residual]),  act as aanet_conv3d_fused_f32.
+ * x [n][d][h][w][c]; residual and out [n][do][ho][wo][co] with do = (d + 1) / 2, ho = (h + 1) / 2,
+ * wo = (w + 1) / 2 (odd and even sizes); channels-last.  Channel sets, pack layout
+ * ([co][c][3][3][3] weight, aanet_conv3d_s2_pack_bytes(co, c) device bytes), status codes and
+ * numerics as aanet_conv3d_fused_f32: AANET_EINVAL for channel counts outside {32, 64, 96, 128},
+ * AANET_EUNSUPPORTED when one image's input or output volume reaches 2^31 bytes. */
+size_t aanet_conv3d_s2_pack_bytes(int co, int c);
+int aanet_conv3d_s2_pack_f32(const float *w, int co, int c, void *wsplit, aanet_stream_t stream);
+int aanet_conv3d_s2_fused_f32(const float *x, const void *wsplit, const float *bias,
+                              const float *residual, int act, float *out, int n, int c, int d,
+                              int h, int w, int co, aanet_stream_t stream);
+/* Host-only: AANET_OK when aanet_conv3d_s2_fused_f32 takes a Conv3d of these parameters (3x3x3,
+ * stride 2, padding 1, dilation 1, one group, c and co in {32, 64, 96, 128}), AANET_EUNSUPPORTED
+ * for any other conv, AANET_EINVAL for a parameter that is not positive (pad: negative). */
+int aanet_conv3d_s2_supported(int c, int co, int kd, int kh, int kw, int stride, int pad, int dil,
+                              int groups);
+
+/* The 3-D aggregators' up-sampling convs in eval (nn.ConvTranspose3d(c, co, 3, stride 2,
+ * padding 1, output_padding 1, bias=False) + BatchNorm3d [+ ReLU], BN folded by the caller):
+ *   out = act(conv_transpose3d(x, W, stride 2, padding 1, output_padding 1) + bias [+ residual]).
+ * x [n][d][h][w][c]; residual and out [n][2d][2h][2w][co]; channels-last.  The pack entry takes
+ * torch's transposed-conv weight layout [c][co][3][3][3].  Every output is computed by one owner
+ * from its 1..8 taps (eight output phases): no col2im, no atomics.  Channel sets, status codes and
+ * numerics as aanet_conv3d_fused_f32 (the 2^31-byte bound applies to the 8x larger output too). */
+size_t aanet_deconv3d2x_pack_bytes(int co, int c);
+int aanet_deconv3d2x_pack_f32(const float *w, int co, int c, void *wsplit, aanet_stream_t stream);
+int aanet_deconv3d2x_fused_f32(const float *x, const void *wsplit, const float *bias,
+                               const float *residual, int act, float *out, int n, int c, int d,
+                               int h, int w, int co, aanet_stream_t stream);
+/* Host-only: AANET_OK when aanet_deconv3d2x_fused_f32 takes a ConvTranspose3d of these parameters
+ * (3x3x3, stride 2, padding 1, output padding 1, dilation 1, one group, c and co in
+ * {32, 64, 96, 128}), AANET_EUNSUPPORTED for any other, AANET_EINVAL for a parameter that is not
+ * positive (pad, out_pad: negative). */
+int aanet_deconv3d2x_supported(int c, int co, int kd, int kh, int kw, int stride, int pad,
+                               int out_pad, int dil, int groups);
+
 /* aanet_conv3x3s2_f32 with the CSA sum of output a in its epilogue (aggregation.py:388-400 for an
  * output branch whose finer-scale term is this conv):
  *   out_a = act_a(conv + bias [+ identity] [+ resize(up)])
