@@ -67,6 +67,10 @@ _SIGNATURES = {
     "aanet_deconv3d2x_pack_f32": [_P, _I, _I, _P, _P],
     "aanet_deconv3d2x_fused_f32": [_P, _P, _P, _P, _I, _P] + [_I] * 6 + [_P],
     "aanet_deconv3d2x_supported": [_I] * 10,
+    "aanet_conv3d_head_f32": [_P, _P, _P, _P, _I, _P] + [_I] * 5 + [_P],
+    "aanet_deconv3d_head_f32": [_P, _P, _P, _P, _I, _P] + [_I] * 5 + [_P],
+    "aanet_conv3d_head_supported": [_I] * 9,
+    "aanet_deconv3d_head_supported": [_I] * 10,
     "aanet_mdcn_im2col_f32": [_P, _P, _P, _P] + [_I] * 9 + [_P],
     "aanet_mdcn_sample_index": [_P, _P, _P, _P] + [_I] * 9 + [_P],
     "aanet_conv_engine_plan": [_P, _P],

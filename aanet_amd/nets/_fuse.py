@@ -158,8 +158,9 @@ def to_ndhwc(x):
     return x if _lib.is_ndhwc(x) else x.contiguous(memory_format=torch.channels_last_3d)
 
 
-# Whether the 3-D convs that stay on MIOpen (one output channel, GC-Net's last transposed conv, and
-# any shape in a SLOWER_THAN_MIOPEN set of ops) are handed
+# Whether the 3-D convs that stay on MIOpen (any shape in a SLOWER_THAN_MIOPEN set of ops, a head
+# followed by a BatchNorm3d, convs outside the kernels' parameter sets; none in the four
+# aggregators since the one-channel heads run on csrc/conv3d_head.hip) are handed
 # channels_last_3d tensors as they come out of the HIP kernel (True) or an NCDHW copy (False: the
 # layout they have always run on).  Measured on the PSMNet hourglass aggregator at the C5 volume
 # (B=8): 150 ms per forward as they come, 182 ms with the copies (22 layout copies, 41 ms;
@@ -172,18 +173,35 @@ def to_ncdhw(x):
     return x.contiguous()
 
 
+def head3d_act(x, conv, act=None, residual=None):
+    """act(conv(x) + bias [+ residual]) of an ops.conv3d_head_ok Conv3d or an ops.deconv3d_head_ok
+    ConvTranspose3d as ONE HIP kernel.  x is channels_last_3d; residual and the result are
+    [N, 1, do, ho, wo] contiguous.  The kernel reads the module's own weight and bias (a copy only
+    when the weight is not contiguous float32), so nothing is cached."""
+    w, b = conv.weight.detach(), conv.bias
+    if w.dtype != torch.float32 or not w.is_contiguous():
+        w = w.float().contiguous()
+    if b is not None:
+        b = b.detach().float()
+    fn = ops.deconv3d_head_fused if isinstance(conv, nn.ConvTranspose3d) else ops.conv3d_head_fused
+    return fn(x, w, b, act, residual)
+
+
 def run_fused_chain3d(mods, x, residual=None):
     """Run a flat module list of a 3-D aggregator in eval: each ops.conv3d_ok (stride 1) or
     ops.conv3d_s2_ok (stride 2) Conv3d or ops.deconv3d2x_ok ConvTranspose3d [+ BatchNorm3d]
-    [+ ReLU | LeakyReLU(0.2)] run of it is ONE HIP kernel on channels_last_3d tensors; anything
-    else (one-channel heads, a transposed conv without output padding) runs as is, on MIOpen.
+    [+ ReLU | LeakyReLU(0.2)] run of it is ONE HIP kernel on channels_last_3d tensors, and so is
+    each one-channel head (ops.conv3d_head_ok Conv3d, ops.deconv3d_head_ok ConvTranspose3d)
+    [+ ReLU | LeakyReLU(0.2)] with no BatchNorm3d behind it; anything else runs as is, on MIOpen.
     residual: added to the LAST conv's BN output when that conv ends the list with no activation
     behind it (the `block(x) + x` adds of the aggregators)."""
     i, n = 0, len(mods)
     while i < n:
         m = mods[i]
         s1 = ops.conv3d_ok(m)
-        if s1 or ops.conv3d_s2_ok(m) or ops.deconv3d2x_ok(m):
+        head = not s1 and (ops.conv3d_head_ok(m) or ops.deconv3d_head_ok(m)) and \
+            not (i + 1 < n and isinstance(mods[i + 1], nn.BatchNorm3d))
+        if s1 or head or ops.conv3d_s2_ok(m) or ops.deconv3d2x_ok(m):
             bn = act = None
             j = i + 1
             if j < n and isinstance(mods[j], nn.BatchNorm3d):
@@ -192,8 +210,11 @@ def run_fused_chain3d(mods, x, residual=None):
                 act, j = act_name(mods[j]), j + 1
             res = None
             if residual is not None and j == n and act is None:
-                res, residual = to_ndhwc(residual), None
-            x = (conv3d_bn_act if s1 else resample3d_bn_act)(to_ndhwc(x), m, bn, act, res)
+                res, residual = (residual.contiguous() if head else to_ndhwc(residual)), None
+            if head:
+                x = head3d_act(to_ndhwc(x), m, act, res)
+            else:
+                x = (conv3d_bn_act if s1 else resample3d_bn_act)(to_ndhwc(x), m, bn, act, res)
             i = j
         else:
             if isinstance(m, (nn.Conv3d, nn.ConvTranspose3d)) and not MIOPEN_NDHWC:

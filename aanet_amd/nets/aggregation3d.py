@@ -13,9 +13,13 @@ the stride-1 convs on csrc/conv3d.hip (ops.conv3d_fused), the stride-2 convs on 
 (ops.conv3d_s2_fused) and the stride-2 transposed convs with output padding 1 on
 csrc/deconv3d.hip (ops.deconv3d2x_fused).  In the PSMNet hourglass conv5's `relu(. + pre)` and
 conv6's `+ cost0` of the enclosing aggregator are residuals of those launches; GC-Net's
-`x + skip` adds follow a ReLU and stay torch adds.  The one-channel heads and GC-Net's
-trans_conv5 (32 -> 1, no output padding) run on PyTorch (MIOpen), as does everything in training,
-under autograd and with `aanet_fuse = False` (the reference op order, unchanged).
+`x + skip` adds follow a ReLU and stay torch adds.  The one-channel heads -- StereoNet's and
+PSMNet-basic's final_conv, the hourglass aggregator's classif1-3[2] and GC-Net's trans_conv5
+(transposed, 32 -> 1, no output padding) -- run on csrc/conv3d_head.hip (ops.conv3d_head_fused /
+ops.deconv3d_head_fused) with the module's own weight and bias; the hourglass aggregator's
+`+ cost1` / `+ cost2` adds are residuals of the classif2 / classif3 head launches.  So in eval no
+conv of a 3-D aggregator runs on PyTorch (MIOpen); everything does in training, under autograd
+and with `aanet_fuse = False` (the reference op order, unchanged).
 """
 import torch
 import torch.nn as nn
@@ -202,8 +206,9 @@ class PSMNetHGAggregation(FoldCacheMixin, nn.Module):
         return [_up4(cost3)]
 
     def _forward_fused(self, cost):
-        """Eval fast path: the same graph with the multi-channel convs on the HIP kernels; the
-        `+ cost0` adds are conv6's residual (a torch add where conv6 stays on MIOpen).  The
+        """Eval fast path: the same graph with every conv on the HIP kernels; the `+ cost0` adds
+        are conv6's residual (a torch add where conv6 stays on MIOpen) and `+ cost1` / `+ cost2`
+        the classif2 / classif3 heads' (a torch add where a head stays on MIOpen).  The
         hourglasses follow this module's decision.  When the MIOpen convs are given NCDHW copies
         (_fuse.MIOPEN_NDHWC off) the hourglass outputs are NCDHW, and the `+ cost0` adds use an
         NCDHW copy of cost0 so that their results are too."""
@@ -216,8 +221,8 @@ class PSMNetHGAggregation(FoldCacheMixin, nn.Module):
         # pre1, as the reference (not pre2)
         out3, _, _ = self.dres4(out2, pre1, post2, fused=True, out_residual=cost0)
         cost1 = _chain(self.classif1, out1)
-        cost2 = _chain(self.classif2, out2) + cost1
-        cost3 = _chain(self.classif3, out3) + cost2
+        cost2 = _chain(self.classif2, out2, residual=cost1)  # `+ cost1` in the head's launch
+        cost3 = _chain(self.classif3, out3, residual=cost2)
         return [_up4(cost3)]
 
 

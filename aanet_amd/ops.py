@@ -934,6 +934,111 @@ def deconv3d2x_fused(x, wsplit, bias, co, act=None, residual=None, out=None):
                              lambda v: 2 * v, x, wsplit, bias, co, act, residual, out)
 
 
+# ------------------------------------- the aggregators' one-channel heads (conv3d_head.hip) ------
+# Input channel counts c the head kernels take but that lost to MIOpen in tools/conv3d_bench.py on
+# the MI355X; conv3d_head_ok / deconv3d_head_ok refuse them so they stay on MIOpen.
+CONV3D_HEAD_SLOWER_THAN_MIOPEN = frozenset()
+DECONV3D_HEAD_SLOWER_THAN_MIOPEN = frozenset()
+
+
+def conv3d_head_supported(c, co=1, kernel=3, stride=1, padding=1, dilation=1, groups=1):
+    """Whether aanet_conv3d_head_f32 takes a Conv3d of these parameters
+    (aanet_conv3d_head_supported): one output channel, 3x3x3, stride 1, padding 1, dilation 1, one
+    group, c in {32, 64, 96, 128}."""
+    kd, kh, kw = (kernel,) * 3 if isinstance(kernel, int) else kernel
+    return _lib.lib().aanet_conv3d_head_supported(c, co, kd, kh, kw, stride, padding, dilation,
+                                                  groups) == 0
+
+
+def deconv3d_head_supported(c, co=1, kernel=3, stride=2, padding=1, output_padding=0, dilation=1,
+                            groups=1):
+    """Whether aanet_deconv3d_head_f32 takes a ConvTranspose3d of these parameters
+    (aanet_deconv3d_head_supported): one output channel, 3x3x3, stride 2, padding 1, output
+    padding 0, dilation 1, one group, c in {32, 64, 96, 128}."""
+    kd, kh, kw = (kernel,) * 3 if isinstance(kernel, int) else kernel
+    return _lib.lib().aanet_deconv3d_head_supported(c, co, kd, kh, kw, stride, padding,
+                                                    output_padding, dilation, groups) == 0
+
+
+def conv3d_head_ok(conv):
+    """A conv module that conv3d_head_fused runs (aanet_conv3d_head_supported and the measured
+    dispatch table): nn.Conv3d or a subclass, zero padding, cubic parameters."""
+    if not isinstance(conv, torch.nn.Conv3d) or conv.padding_mode != "zeros" or \
+            isinstance(conv.padding, str):
+        return False
+    vals = _cubic(conv, ("stride", "padding", "dilation"))
+    c, co = conv.in_channels, conv.out_channels
+    return vals is not None and \
+        conv3d_head_supported(c, co, tuple(conv.kernel_size), *vals, conv.groups) and \
+        c not in CONV3D_HEAD_SLOWER_THAN_MIOPEN
+
+
+def deconv3d_head_ok(conv):
+    """A transposed conv module that deconv3d_head_fused runs (aanet_deconv3d_head_supported and
+    the measured dispatch table): nn.ConvTranspose3d or a subclass, cubic parameters."""
+    if not isinstance(conv, torch.nn.ConvTranspose3d) or conv.padding_mode != "zeros":
+        return False
+    vals = _cubic(conv, ("stride", "padding", "output_padding", "dilation"))
+    c, co = conv.in_channels, conv.out_channels
+    return vals is not None and \
+        deconv3d_head_supported(c, co, tuple(conv.kernel_size), *vals, conv.groups) and \
+        c not in DECONV3D_HEAD_SLOWER_THAN_MIOPEN
+
+
+def _head3d_fused(name, up, x, weight, bias, act, residual, out):
+    """The checks and the launch of the two head ops; up: the transposed head."""
+    for nm, t in (("x", x), ("weight", weight), ("bias", bias), ("residual", residual), ("out", out)):
+        if t is not None and not t.is_cuda:
+            raise NotImplementedError(
+                f"aanet_amd ops run only on the MI355X (HIP) device; {nm} is on {t.device}")
+    if x.dim() != 5:
+        raise ValueError(f"{name}: x must be [N, C, D, H, W]")
+    N, C, D, H, W = x.shape
+    if x.dtype != torch.float32 or not _lib.is_ndhwc(x):
+        raise ValueError(f"{name}: x must be a channels_last_3d float32 tensor")
+    wshape = (C, 1, 3, 3, 3) if up else (1, C, 3, 3, 3)
+    if weight.dtype != torch.float32 or tuple(weight.shape) != wshape or \
+            not weight.is_contiguous() or weight.device != x.device:
+        raise ValueError(f"{name}: weight must be a contiguous float32 tensor of shape {wshape} "
+                         f"on {x.device}")
+    if not (deconv3d_head_supported if up else conv3d_head_supported)(C):
+        raise ValueError(f"{name}: {C} input channels are outside the kernel (32, 64, 96, 128)")
+    shape = (N, 1) + tuple(2 * v - 1 if up else v for v in (D, H, W))
+    for nm, t in (("residual", residual), ("out", out)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or \
+                t.device != x.device:
+            raise ValueError(f"{name}: {nm} must be a contiguous float32 tensor of shape {shape} "
+                             f"on {x.device}")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (1,) or
+                             bias.device != x.device):
+        raise ValueError(f"{name}: bias must be a float32 tensor of shape (1,) on {x.device}")
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=x.dtype)
+    if x.numel() == 0:
+        return out
+    call("aanet_deconv3d_head_f32" if up else "aanet_conv3d_head_f32", ptr(x), ptr(weight),
+         ptr(bias), ptr(residual), ACT[act], ptr(out), N, C, D, H, W, stream_of(x))
+    return out
+
+
+def conv3d_head_fused(x, weight, bias, act=None, residual=None, out=None):
+    """act(conv3d(x, weight, stride 1, padding 1) + bias [+ residual]) for a one-output-channel
+    3x3x3 conv (aanet_conv3d_head_f32).  x [N, C, D, H, W] is channels_last_3d float32; weight is
+    the module's own contiguous [1, C, 3, 3, 3] (no pack); bias is a (1,) tensor or None; residual
+    and the result (the caller's `out` when given) are contiguous [N, 1, D, H, W]."""
+    return _head3d_fused("conv3d_head_fused", False, x, weight, bias, act, residual, out)
+
+
+def deconv3d_head_fused(x, weight, bias, act=None, residual=None, out=None):
+    """act(conv_transpose3d(x, weight, stride 2, padding 1, output_padding 0) + bias [+ residual])
+    for a one-output-channel 3x3x3 transposed conv (aanet_deconv3d_head_f32).  x [N, C, D, H, W]
+    is channels_last_3d float32; weight is the module's own contiguous [C, 1, 3, 3, 3]; residual
+    and the result (the caller's `out` when given) are contiguous [N, 1, 2D-1, 2H-1, 2W-1]."""
+    return _head3d_fused("deconv3d_head_fused", True, x, weight, bias, act, residual, out)
+
+
 def csa_sum(inputs, act="leaky"):
     """act(inputs[0] + resize(inputs[1]) + ...) at inputs[0]'s size (aggregation.py:387-400)."""
     require_gpu(*inputs)

@@ -424,6 +424,37 @@ int aanet_deconv3d2x_fused_f32(const float *x, const void *wsplit, const float *
 int aanet_deconv3d2x_supported(int c, int co, int kd, int kh, int kw, int stride, int pad,
                                int out_pad, int dil, int groups);
 
+/* The 3-D aggregators' one-output-channel heads in eval (nets/aggregation.py: StereoNet's and
+ * PSMNet-basic's final_conv, the hourglass aggregator's classif1-3[2]: nn.Conv3d(c, 1, 3,
+ * padding 1); GC-Net's trans_conv5: nn.ConvTranspose3d(c, 1, 3, stride 2, padding 1)):
+ *   aanet_conv3d_head_f32:    out = act(conv3d(x, W, stride 1, padding 1) + bias [+ residual]),
+ *                             out [n][1][d][h][w];
+ *   aanet_deconv3d_head_f32:  out = act(conv_transpose3d(x, W, stride 2, padding 1,
+ *                             output_padding 0) + bias [+ residual]), out [n][1][2d-1][2h-1][2w-1].
+ * x [n][d][h][w][c] channels-last, c in {32, 64, 96, 128}; residual (may be NULL) and out are
+ * contiguous (with one channel NCDHW and NDHWC are the same bytes); bias: ONE device float or
+ * NULL; act as aanet_conv3d_fused_f32.  w is the module's own fp32 weight, w[ci * 27 + kd * 9 +
+ * kh * 3 + kw] -- a Conv3d [1][c][3][3][3] and a ConvTranspose3d [c][1][3][3][3] are the same
+ * bytes -- so there is no pack entry.  Exact-fp32 MFMA contraction (no bf16 split); every output
+ * has one owner (no atomics), and its summation order does not depend on the batch.  No
+ * allocation or synchronisation (HIP-graph capturable).  AANET_EINVAL for a null x / w / out, a
+ * size <= 0, act outside 0..2 or c outside the set -- checked on the host before any launch;
+ * AANET_EUNSUPPORTED when one image's input or output volume reaches 2^31 bytes. */
+int aanet_conv3d_head_f32(const float *x, const float *w, const float *bias, const float *residual,
+                          int act, float *out, int n, int c, int d, int h, int w_,
+                          aanet_stream_t stream);
+int aanet_deconv3d_head_f32(const float *x, const float *w, const float *bias,
+                            const float *residual, int act, float *out, int n, int c, int d, int h,
+                            int w_, aanet_stream_t stream);
+/* Host-only: AANET_OK when the head entry takes a conv of these parameters (co = 1, 3x3x3, one
+ * group, dilation 1, padding 1, c in {32, 64, 96, 128}; aanet_conv3d_head_supported: stride 1;
+ * aanet_deconv3d_head_supported: stride 2 and output padding 0), AANET_EUNSUPPORTED for any other
+ * conv, AANET_EINVAL for a parameter that is not positive (pad, out_pad: negative). */
+int aanet_conv3d_head_supported(int c, int co, int kd, int kh, int kw, int stride, int pad, int dil,
+                                int groups);
+int aanet_deconv3d_head_supported(int c, int co, int kd, int kh, int kw, int stride, int pad,
+                                  int out_pad, int dil, int groups);
+
 /* aanet_conv3x3s2_f32 with the CSA sum of output a in its epilogue (aggregation.py:388-400 for an
  * output branch whose finer-scale term is this conv):
  *   out_a = act_a(conv + bias [+ identity] [+ resize(up)])
