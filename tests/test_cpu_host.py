@@ -30,6 +30,77 @@ def test_library_exports_every_header_symbol():
     assert set(fns) == set(_lib.exported_symbols())
 
 
+def header_prototypes():
+    """{name: (return kind, [parameter kinds])} of every aanet_* prototype in the header, comments
+    stripped.  Kinds: "ptr" (anything with a * or an aanet_stream_t), "int", "long", "float",
+    "size_t"."""
+    txt = open(os.path.join(REPO, "include", "aanet_mi355x.h")).read()
+    txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", " ", txt)
+
+    def kind(decl, what):
+        decl = " ".join(decl.split())
+        if "*" in decl or re.search(r"\baanet_stream_t\b", decl):
+            return "ptr"
+        words = [w for w in re.findall(r"[A-Za-z_]\w*", decl) if w not in ("const", "unsigned")]
+        for k in ("size_t", "long", "int", "float"):
+            if words and words[0] == k:
+                return k
+        raise AssertionError(f"{what}: cannot classify '{decl}'")
+
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\n]*?[\s*]+)(aanet_[a-z0-9_]+)\s*\(([^()]*)\)\s*;",
+                                        txt):
+        assert name not in protos, f"{name} declared twice"
+        params = params.strip()
+        plist = [] if params in ("", "void") else [kind(p, name) for p in params.split(",")]
+        protos[name] = (kind(ret, name), plist)
+    return protos
+
+
+_CTYPE_KIND = {ctypes.c_void_p: "ptr", ctypes.c_char_p: "ptr", ctypes.c_int: "int",
+               ctypes.c_long: "long", ctypes.c_float: "float", ctypes.c_size_t: "size_t"}
+
+
+def test_ctypes_argument_lists_match_the_header():
+    """Every aanet_* prototype's parameter kinds, in order, equal the ctypes argtypes the package
+    binds for that name (_lib._SIGNATURES, _lib._SIZE_FUNCTIONS, aanet_status_string in
+    _lib.lib()), and the return kinds agree.  An int that became a long, or an argument added on
+    one side only, shifts every later argument without any symbol name changing."""
+    # ctypes.c_size_t is an alias of c_ulong here: distinguish by identity first, and make sure the
+    # table cannot mistake a long for a size_t
+    assert ctypes.c_size_t is not ctypes.c_long and ctypes.c_int is not ctypes.c_long
+    protos = header_prototypes()
+    assert set(protos) == set(header_functions())
+    bound = {name: ("int", argtypes) for name, argtypes in _lib._SIGNATURES.items()}
+    for name, argtypes, restype in _lib._SIZE_FUNCTIONS:
+        assert name not in bound
+        bound[name] = (_CTYPE_KIND[restype], argtypes)
+    L = _lib.lib()
+    bound["aanet_status_string"] = (_CTYPE_KIND[L.aanet_status_string.restype],
+                                    list(L.aanet_status_string.argtypes))
+    assert set(bound) == set(protos)
+    assert len(protos) >= 63
+    for name, (ret, params) in sorted(protos.items()):
+        bret, argtypes = bound[name]
+        assert [_CTYPE_KIND[a] for a in argtypes] == params, \
+            f"{name}: header {params} != ctypes {[_CTYPE_KIND[a] for a in argtypes]}"
+        assert bret == ret, f"{name}: header returns {ret}, bound as {bret}"
+        # and what lib() actually set on the loaded symbol is that list
+        f = getattr(L, name)
+        assert list(f.argtypes or []) == list(argtypes), name
+        assert _CTYPE_KIND[f.restype] == ret, name
+    # the parser itself, on the prototypes whose kinds are least uniform
+    p = protos
+    assert p["aanet_version"] == ("int", [])
+    assert p["aanet_status_string"] == ("ptr", ["int"])
+    assert p["aanet_conv_weight_pack_split_bytes"] == ("long", ["int"] * 5)
+    assert p["aanet_conv3x3s2_pack_bytes"] == ("size_t", ["int", "int"])
+    assert p["aanet_mdcn_fwd_fused_f32"][1][:7] == ["ptr", "ptr", "long", "ptr", "long", "int", "float"]
+    assert p["aanet_resize_bilinear_f32"][1] == ["ptr", "ptr", "long"] + ["int"] * 4 + ["ptr"]
+    assert p["aanet_mdcn_bwd_algo_f32"][1][-3:] == ["ptr", "size_t", "ptr"]
+
+
 def test_library_version_and_status_strings():
     L = _lib.lib()
     assert L.aanet_version() == _lib.ABI_VERSION == 4
