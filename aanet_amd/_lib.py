@@ -25,11 +25,14 @@ _SIGNATURES = {
     "aanet_corr_volume_bwd_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "aanet_concat_volume_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "aanet_diff_volume_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "aanet_concat_volume_ndhwc_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "aanet_diff_volume_ndhwc_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "aanet_concat_volume_bwd_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "aanet_diff_volume_bwd_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "aanet_corr_pyramid_f32": [_I, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "aanet_disp_regress_f32": [_P, _P, _I, _I, _I, _I, _I, _P],
     "aanet_disp_regress_bwd_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "aanet_disp_regress_up4_f32": [_P, _P, _I, _I, _I, _I, _I, _P],
     "aanet_disp_warp_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "aanet_disp_warp_bwd_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "aanet_mdcn_fwd_f32": [_P, _P, _P, _P, _P, _P] + [_I] * 12 + [_P],

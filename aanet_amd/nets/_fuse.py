@@ -168,6 +168,18 @@ def to_ndhwc(x):
 MIOPEN_NDHWC = True
 
 
+# The two ends of the 3-D path in eval (AANet.cost_volume_construction /
+# AANet.aggregation_and_disparity), one switch each for tests and A/B runs:
+# VOLUME_NDHWC: the concat / difference volume is written channels_last_3d by
+#   csrc/cost_volume_ndhwc.hip (True) or NCDHW and copied by the first conv's to_ndhwc (False);
+# REGRESS_UP4: the PSMNet aggregators hand over their low-resolution cost and
+#   ops.disp_regress_up4 upsamples inside the soft-argmin (True), or F.interpolate writes the
+#   [B, 4D, 4H, 4W] volume and ops.disp_regress reads it back (False).
+# Measured at C5 (B=8): profiles/c5_model_volume_ends.txt.
+VOLUME_NDHWC = True
+REGRESS_UP4 = True
+
+
 def to_ncdhw(x):
     """x as an NCDHW-contiguous tensor (a copy unless it already is one)."""
     return x.contiguous()

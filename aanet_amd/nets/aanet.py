@@ -14,7 +14,9 @@ from .aggregation import AdaptiveAggregation
 from .aggregation3d import (GCNetAggregation, PSMNetBasicAggregation, PSMNetHGAggregation,
                             StereoNetAggregation)
 from .cost import CostVolume, CostVolumePyramid
-from ._fuse import FoldCacheMixin
+from . import _fuse
+from ._fuse import FoldCacheMixin, use_fused
+from .. import ops
 from .estimation import DisparityEstimation
 from .options import get_option, set_options
 from .feature import (FeaturePyramidNetwork, FeaturePyrmaid, GANetFeature, GCNetFeature,
@@ -25,6 +27,9 @@ from .._precision import fp32_convs
 
 _REFINEMENT = {'stereonet': StereoNetRefinement, 'stereodrnet': StereoDRNetRefinement,
                'hourglass': HourglassRefinement}
+
+
+_AGG3D = (GCNetAggregation, PSMNetBasicAggregation, PSMNetHGAggregation, StereoNetAggregation)
 
 
 class AANet(FoldCacheMixin, nn.Module):
@@ -124,7 +129,15 @@ class AANet(FoldCacheMixin, nn.Module):
         return feature
 
     def cost_volume_construction(self, left_feature, right_feature):
-        """aanet.py:146-154."""
+        """aanet.py:146-154.  On the fused eval path a 3-D aggregator's concat / difference
+        volume is written channels_last_3d, as its first conv kernel reads it."""
+        if isinstance(self.cost_volume, CostVolume) and \
+                self.cost_volume.feature_similarity in ('concat', 'difference') and \
+                isinstance(self.aggregation, _AGG3D) and _fuse.VOLUME_NDHWC and \
+                use_fused(self.aggregation, left_feature) and \
+                ops.shift_volume_ndhwc_ok(left_feature.shape[1],
+                                          self.cost_volume.feature_similarity == 'concat'):
+            return self.cost_volume(left_feature, right_feature, channels_last=True)
         cost_volume = self.cost_volume(left_feature, right_feature)
         if isinstance(cost_volume, list):
             if self.num_scales == 1:
@@ -138,6 +151,31 @@ class AANet(FoldCacheMixin, nn.Module):
         if isinstance(aggregation, list):
             return [self.disparity_estimation(a) for a in reversed(aggregation)]
         return [self.disparity_estimation(aggregation)]
+
+    def aggregation_and_disparity(self, cost_volume):
+        """aanet.py:216-224: aggregation + soft-argmin -> the hot-path disparities, coarse to
+        fine.  In eval without autograd the tails are fused: the adaptive aggregator's final_conv
+        + soft-argmin in its last kernel, the PSMNet aggregators' x4 upsampling inside the
+        soft-argmin (ops.disp_regress_up4 on their low-resolution cost).  Training, autograd and
+        `aanet_fuse = False` run the reference op order."""
+        if isinstance(self.aggregation, AdaptiveAggregation):
+            # eval, one output scale: final_conv + the soft-argmin may run in the last tail
+            # kernel's epilogue (AdaptiveAggregation._run)
+            regress = (not self.aggregation.intermediate_supervision and not self.training and
+                       self.disparity_estimation.match_similarity)
+            aggregation, disp = self.aggregation._run(
+                cost_volume, regress=regress, chains=get_option(self.aggregation, "batch_chains"))
+            if disp is not None:
+                return [disp]
+        elif isinstance(self.aggregation, (PSMNetBasicAggregation, PSMNetHGAggregation)) and \
+                _fuse.REGRESS_UP4 and use_fused(self.aggregation, cost_volume) and \
+                ops.disp_regress_up4_ok(cost_volume.shape[2]):
+            cost = self.aggregation(cost_volume, upsample=False)[0]
+            return [ops.disp_regress_up4(cost.squeeze(1).contiguous(),
+                                         negate=not self.disparity_estimation.match_similarity)]
+        else:
+            aggregation = self.aggregation(cost_volume)
+        return self.disparity_computation(aggregation)
 
     def disparity_refinement(self, left_img, right_img, disparity):
         """aanet.py:169-209: refinement i runs at 1/2**(num_downsample-1-i) of the image."""
@@ -164,16 +202,6 @@ class AANet(FoldCacheMixin, nn.Module):
         left_feature = self.feature_extraction(left_img)
         right_feature = self.feature_extraction(right_img)
         cost_volume = self.cost_volume_construction(left_feature, right_feature)
-        disp = None
-        if isinstance(self.aggregation, AdaptiveAggregation):
-            # eval, one output scale: final_conv + the soft-argmin may run in the last tail
-            # kernel's epilogue (AdaptiveAggregation._run)
-            regress = (not self.aggregation.intermediate_supervision and not self.training and
-                       self.disparity_estimation.match_similarity)
-            aggregation, disp = self.aggregation._run(
-                cost_volume, regress=regress, chains=get_option(self.aggregation, "batch_chains"))
-        else:
-            aggregation = self.aggregation(cost_volume)
-        disparity_pyramid = [disp] if disp is not None else self.disparity_computation(aggregation)
+        disparity_pyramid = self.aggregation_and_disparity(cost_volume)
         disparity_pyramid += self.disparity_refinement(left_img, right_img, disparity_pyramid[-1])
         return disparity_pyramid

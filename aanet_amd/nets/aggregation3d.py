@@ -20,6 +20,11 @@ ops.deconv3d_head_fused) with the module's own weight and bias; the hourglass ag
 `+ cost1` / `+ cost2` adds are residuals of the classif2 / classif3 head launches.  So in eval no
 conv of a 3-D aggregator runs on PyTorch (MIOpen); everything does in training, under autograd
 and with `aanet_fuse = False` (the reference op order, unchanged).
+
+The two ends: in a fused AANet the volume arrives channels_last_3d from csrc/cost_volume_ndhwc.hip
+(no layout copy in front of the first conv), and the PSMNet aggregators called with
+`upsample=False` return their low-resolution cost for ops.disp_regress_up4, which upsamples x4
+inside the soft-argmin (nets/aanet.py aggregation_and_disparity; switches in nets/_fuse.py).
 """
 import torch
 import torch.nn as nn
@@ -73,6 +78,12 @@ def _up4(cost):
                                        align_corners=False), 1)
 
 
+def _low_res_only():
+    return ValueError("upsample=False is the fused eval path's (eval mode, no autograd, HIP "
+                      "device, aanet_fuse on): this call runs the reference op order, which "
+                      "always upsamples")
+
+
 class StereoNetAggregation(FoldCacheMixin, nn.Module):
     """aggregation.py:69-90: four conv3d blocks + a 1-channel Conv3d -> [B, D, H, W]."""
 
@@ -107,12 +118,17 @@ class PSMNetBasicAggregation(FoldCacheMixin, nn.Module):
         self.classify = nn.Sequential(conv1, relu(), final_conv)
 
     @fp32_convs
-    def forward(self, cost):
+    def forward(self, cost, upsample=True):
+        """upsample=False (fused eval path only, else ValueError): the low-resolution
+        [B, 1, D, H, W] cost in a one-element list, for ops.disp_regress_up4."""
         if use_fused(self, cost):
             cost0 = _chain(self.dres0, cost)
             for name in ("dres1", "dres2", "dres3", "dres4"):
                 cost0 = _chain(getattr(self, name), cost0, residual=cost0)
-            return [_up4(_chain(self.classify, cost0))]
+            low = _chain(self.classify, cost0)
+            return [_up4(low)] if upsample else [low]
+        if not upsample:
+            raise _low_res_only()
         cost0 = self.dres0(cost)
         for name in ("dres1", "dres2", "dres3", "dres4"):
             cost0 = getattr(self, name)(cost0) + cost0
@@ -187,9 +203,13 @@ class PSMNetHGAggregation(FoldCacheMixin, nn.Module):
                 nn.Conv3d(32, 1, kernel_size=3, padding=1, stride=1, bias=False)))
 
     @fp32_convs
-    def forward(self, cost):
+    def forward(self, cost, upsample=True):
+        """upsample=False (fused eval path only, else ValueError): the low-resolution
+        [B, 1, D, H, W] cost in a one-element list, for ops.disp_regress_up4."""
         if use_fused(self, cost):
-            return self._forward_fused(cost)
+            return self._forward_fused(cost, upsample)
+        if not upsample:
+            raise _low_res_only()
         cost0 = self.dres0(cost)
         cost0 = self.dres1(cost0) + cost0
         out1, pre1, post1 = self.dres2(cost0, None, None, fused=False)
@@ -205,7 +225,7 @@ class PSMNetHGAggregation(FoldCacheMixin, nn.Module):
             return [_up4(cost1), _up4(cost2), _up4(cost3)]
         return [_up4(cost3)]
 
-    def _forward_fused(self, cost):
+    def _forward_fused(self, cost, upsample=True):
         """Eval fast path: the same graph with every conv on the HIP kernels; the `+ cost0` adds
         are conv6's residual (a torch add where conv6 stays on MIOpen) and `+ cost1` / `+ cost2`
         the classif2 / classif3 heads' (a torch add where a head stays on MIOpen).  The
@@ -223,7 +243,7 @@ class PSMNetHGAggregation(FoldCacheMixin, nn.Module):
         cost1 = _chain(self.classif1, out1)
         cost2 = _chain(self.classif2, out2, residual=cost1)  # `+ cost1` in the head's launch
         cost3 = _chain(self.classif3, out3, residual=cost2)
-        return [_up4(cost3)]
+        return [_up4(cost3)] if upsample else [cost3]
 
 
 class GCNetAggregation(FoldCacheMixin, nn.Module):

@@ -16,14 +16,18 @@ class CostVolume(nn.Module):
         self.max_disp = max_disp
         self.feature_similarity = feature_similarity
 
-    def forward(self, left_feature, right_feature):
-        """nets/cost.py:19-55: [B,D,H,W] (correlation) or [B,C',D,H,W] (concat / difference)."""
+    def forward(self, left_feature, right_feature, channels_last=False):
+        """nets/cost.py:19-55: [B,D,H,W] (correlation) or [B,C',D,H,W] (concat / difference).
+        channels_last (concat / difference only): the 5-D volume comes out channels_last_3d, as
+        the 3-D conv kernels read it (same values)."""
         if self.feature_similarity == 'correlation':
             return CorrelationVolumeFunction.apply(left_feature, right_feature, self.max_disp)
         if self.feature_similarity == 'concat':
-            return ShiftVolumeFunction.apply(left_feature, right_feature, self.max_disp, True)
+            return ShiftVolumeFunction.apply(left_feature, right_feature, self.max_disp, True,
+                                             channels_last)
         if self.feature_similarity == 'difference':
-            return ShiftVolumeFunction.apply(left_feature, right_feature, self.max_disp, False)
+            return ShiftVolumeFunction.apply(left_feature, right_feature, self.max_disp, False,
+                                             channels_last)
         raise NotImplementedError
 
 

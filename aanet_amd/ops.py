@@ -53,13 +53,41 @@ def corr_pyramid(lefts, rights, max_disp):
     return outs
 
 
-def shift_volume(left, right, max_disp, concat):
-    """nets/cost.py:22-38 (difference / concat) -> [B, C', D, H, W]."""
+# Feature channel counts c at which the channels-last volume kernel lost to the NCDHW kernel plus
+# the layout copy in tools/volume_ends_bench.py on the MI355X, as (c, concat) pairs: the models
+# keep the NCDHW kernel + copy for them (profiles/volume_ends_bench.txt names each).
+SHIFT_VOLUME_NDHWC_SLOWER = frozenset()
+
+
+def shift_volume_ndhwc_ok(c, concat):
+    """Whether the models write the concat / difference volume of c-channel features
+    channels-last (the measured dispatch table; the kernel itself takes any c)."""
+    return (int(c), bool(concat)) not in SHIFT_VOLUME_NDHWC_SLOWER
+
+
+def shift_volume(left, right, max_disp, concat, channels_last=False, out=None):
+    """nets/cost.py:22-38 (difference / concat) -> [B, C', D, H, W].  channels_last: the result is
+    channels_last_3d (stored [B][D][H][W][C'], what the 3-D conv kernels read in place), written
+    by csrc/cost_volume_ndhwc.hip; same values.  out: a caller-owned result of that shape, dense in
+    the format asked for."""
     require_gpu(left, right, names=("left", "right"))
     B, C, H, W = left.shape
+    if right.shape != left.shape:
+        raise ValueError("left/right feature shapes differ")
     oc = 2 * C if concat else C
-    out = torch.empty((B, oc, max_disp, H, W), device=left.device, dtype=left.dtype)
-    name = "aanet_concat_volume_f32" if concat else "aanet_diff_volume_f32"
+    shape = (B, oc, max_disp, H, W)
+    if out is None:
+        out = torch.empty(shape, device=left.device, dtype=left.dtype,
+                          memory_format=torch.channels_last_3d if channels_last
+                          else torch.contiguous_format)
+    else:
+        if tuple(out.shape) != shape or out.dtype != left.dtype or out.device != left.device:
+            raise ValueError(f"out must be a {left.dtype} tensor of shape {shape} on {left.device}")
+        if not (_lib.is_ndhwc(out) if channels_last else out.is_contiguous()):
+            raise ValueError("out must be " + ("channels_last_3d-contiguous (channels_last=True)"
+                                               if channels_last else "contiguous"))
+    name = ("aanet_concat_volume" if concat else "aanet_diff_volume") + \
+        ("_ndhwc_f32" if channels_last else "_f32")
     call(name, ptr(left), ptr(right), ptr(out), B, C, H, W, max_disp, stream_of(left))
     return out
 
@@ -120,11 +148,14 @@ class CorrelationPyramidFunction(Function):
 
 
 class ShiftVolumeFunction(Function):
+    """apply(left, right, max_disp, concat, channels_last=False); the backward takes a gradient of
+    either layout (made contiguous)."""
+
     @staticmethod
-    def forward(ctx, left, right, max_disp, concat):
+    def forward(ctx, left, right, max_disp, concat, channels_last=False):
         left, right = left.contiguous(), right.contiguous()
         ctx.shape, ctx.max_disp, ctx.concat = left.shape, max_disp, concat
-        return shift_volume(left, right, max_disp, concat)
+        return shift_volume(left, right, max_disp, concat, channels_last)
 
     @staticmethod
     @once_differentiable
@@ -136,7 +167,7 @@ class ShiftVolumeFunction(Function):
         gr = grad_out.new_empty((B, C, H, W))
         name = "aanet_concat_volume_bwd_f32" if ctx.concat else "aanet_diff_volume_bwd_f32"
         call(name, ptr(grad_out), ptr(gl), ptr(gr), B, C, H, W, ctx.max_disp, stream_of(grad_out))
-        return gl, gr, None, None
+        return gl, gr, None, None, None
 
 
 # ------------------------------------------------------------ disparity regression ------
@@ -147,6 +178,43 @@ def disp_regress(cost, negate=False, out=None):
     if out is None:
         out = torch.empty((B, H, W), device=cost.device, dtype=cost.dtype)
     call("aanet_disp_regress_f32", ptr(cost), ptr(out), B, D, H, W, int(bool(negate)),
+         stream_of(cost))
+    return out
+
+
+# Coarse disparity counts d at which the fused kernel lost to F.interpolate + disp_regress in
+# tools/volume_ends_bench.py on the MI355X: the models keep the two-op tail for them
+# (profiles/volume_ends_bench.txt names each).
+REGRESS_UP4_SLOWER = frozenset()
+
+
+def disp_regress_up4_ok(d):
+    """Whether the models run the fused x4-upsampling soft-argmin on a d-plane cost (the measured
+    dispatch table; the kernel itself takes any d)."""
+    return int(d) not in REGRESS_UP4_SLOWER
+
+
+def disp_regress_up4(cost, negate=False, out=None):
+    """disp_regress(F.interpolate(cost[:, None], scale_factor=4, mode='trilinear',
+    align_corners=False)[:, 0], negate) as ONE kernel (csrc/regression_up4.hip): cost [B, D, H, W]
+    -> [B, 4H, 4W] over the candidates 0 .. 4D-1; the upsampled volume is never stored.  Forward
+    only: the tail of the PSMNet aggregators in eval."""
+    if cost.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("disp_regress_up4 is forward-only (no autograd): call it under "
+                           "torch.no_grad() or on a detached cost; for gradients use "
+                           "F.interpolate followed by DisparityRegressionFunction")
+    require_gpu(cost, names=("cost",))
+    if cost.dim() != 4:
+        raise ValueError(f"cost must be [B, D, H, W], got {tuple(cost.shape)}")
+    B, D, H, W = cost.shape
+    shape = (B, 4 * H, 4 * W)
+    if out is None:
+        out = torch.empty(shape, device=cost.device, dtype=cost.dtype)
+    elif tuple(out.shape) != shape or out.dtype != cost.dtype or out.device != cost.device or \
+            not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {cost.dtype} tensor of shape {shape} on "
+                         f"{cost.device}")
+    call("aanet_disp_regress_up4_f32", ptr(cost), ptr(out), B, D, H, W, int(bool(negate)),
          stream_of(cost))
     return out
 

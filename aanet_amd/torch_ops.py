@@ -172,5 +172,19 @@ def _regress_backward_formula(ctx, grad_disp):
 torch.library.register_autograd(f"{_NS}::disp_regress", _regress_backward_formula,
                                 setup_context=_regress_setup)
 
+
+@torch.library.custom_op(f"{_NS}::disp_regress_up4", mutates_args=(), device_types="cuda")
+def disp_regress_up4(cost: Tensor, negate: bool) -> Tensor:
+    """x4 trilinear upsampling + soft-argmin in one kernel (ops.disp_regress_up4) -> [B, 4H, 4W].
+    Forward only: no autograd formula is registered."""
+    return ops.disp_regress_up4(cost.detach().contiguous(), negate)
+
+
+@disp_regress_up4.register_fake
+def _(cost, negate):
+    B, _, H, W = cost.shape
+    return cost.new_empty((B, 4 * H, 4 * W))
+
+
 OPS = ("mdcn_forward", "mdcn_backward", "corr_volume", "corr_volume_backward", "disp_regress",
-       "disp_regress_backward")
+       "disp_regress_backward", "disp_regress_up4")

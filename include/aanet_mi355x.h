@@ -87,6 +87,17 @@ int aanet_concat_volume_f32(const float *left, const float *right, float *out, i
 int aanet_diff_volume_f32(const float *left, const float *right, float *out, int n, int c, int h,
                           int w, int max_disp, aanet_stream_t stream);
 
+/* The two volumes above written channels-last: out is stored [n][max_disp][h][w][oc] with oc
+ * innermost (oc = 2c for concat, c for difference), i.e. the memory of a [n, oc, max_disp, h, w]
+ * tensor in torch.channels_last_3d, which the 3-D conv kernels below read in place.  Same values
+ * as the NCDHW entries, bit for bit; any c, h, w, max_disp >= 1 (c % 4 == 0 and a 16-byte aligned
+ * out take the vector kernel, csrc/cost_volume_ndhwc.hip).  Forward only: the NCDHW backward
+ * entries take the gradient of either layout once it is made contiguous. */
+int aanet_concat_volume_ndhwc_f32(const float *left, const float *right, float *out, int n, int c,
+                                  int h, int w, int max_disp, aanet_stream_t stream);
+int aanet_diff_volume_ndhwc_f32(const float *left, const float *right, float *out, int n, int c,
+                                int h, int w, int max_disp, aanet_stream_t stream);
+
 /* Autograd of concat / difference: grad_left / grad_right [n,c,h,w] OVERWRITTEN. */
 int aanet_concat_volume_bwd_f32(const float *grad_out, float *grad_left, float *grad_right, int n,
                                 int c, int h, int w, int max_disp, aanet_stream_t stream);
@@ -110,6 +121,13 @@ int aanet_disp_regress_f32(const float *cost, float *disp, int n, int d, int h, 
 /* Autograd of the above: grad_cost [n, d, h, w] OVERWRITTEN. */
 int aanet_disp_regress_bwd_f32(const float *cost, const float *grad_disp, float *grad_cost, int n,
                                int d, int h, int w, int negate, aanet_stream_t stream);
+
+/* x4 trilinear upsampling (align_corners = false) fused into the soft-argmin, the tail of the
+ * PSMNet aggregators (nets/aggregation.py:136, 252): cost [n, d, h, w] -> disp [n, 4h, 4w],
+ * disp = sum_i i * softmax_i(+-up4(cost)) over the 4d candidates of the upsampled volume, which is
+ * never stored.  Forward only; any d, h, w >= 1 (csrc/regression_up4.hip). */
+int aanet_disp_regress_up4_f32(const float *cost, float *disp, int n, int d, int h, int w,
+                               int negate, aanet_stream_t stream);
 
 /* ------------------------------------------------------------ disparity warp ----------- */
 

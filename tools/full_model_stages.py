@@ -20,7 +20,6 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from aanet_amd.nets import AANet  # noqa: E402
-from aanet_amd.nets.aggregation import AdaptiveAggregation  # noqa: E402
 from aanet_amd.nets.deform import DeformConv2d  # noqa: E402
 
 name = sys.argv[1] if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else "aanet"
@@ -62,13 +61,7 @@ def stages(m):
         st["cv"] = m.cost_volume_construction(st["lf"], st["rf"])
 
     def agg():
-        if not isinstance(m.aggregation, AdaptiveAggregation):  # 3-D aggregators (C5)
-            st["disp"] = m.disparity_computation(m.aggregation(st["cv"]))
-            return
-        regress = (not m.aggregation.intermediate_supervision and not m.training and
-                   m.disparity_estimation.match_similarity)
-        a, d = m.aggregation._run(st["cv"], regress=regress)
-        st["disp"] = [d] if d is not None else m.disparity_computation(a)
+        st["disp"] = m.aggregation_and_disparity(st["cv"])
 
     def refine():
         st["out"] = m.disparity_refinement(left, right, st["disp"][-1])
