@@ -30,22 +30,13 @@
 
 namespace {
 
-constexpr int NT = 256;                     // 4 waves, two tile rows each
+constexpr int NT = C3_NT;                   // 4 waves, two tile rows each
 constexpr int TR = 8, TC = 16;              // output tile (h x w)
 constexpr int HWW = TC + 2, HR = TR + 2;    // halo
 constexpr int NPOS = HR * HWW;              // 180 positions
 constexpr int PE = NPOS * 32;               // bf16 per piece plane
 constexpr int HIT = (NPOS * 4 + NT - 1) / NT;  // halo octets (8 channels of a position) per thread
 constexpr unsigned OOB = C3_OOB;
-
-struct C3Args {
-  const float *x;      // [N][D][H][W][C]
-  const bf16x8 *wsplit;  // [Co/32][C/32][9 (kh,kw)][3 kd][2 co blocks][3 pieces][64 lanes] x 16 B
-  const float *bias;   // [Co] or NULL
-  const float *res;    // [N][D][H][W][Co] or NULL
-  float *out;          // [N][D][H][W][Co]
-  int N, C, D, H, W, Co, act;
-};
 
 __global__ __launch_bounds__(NT, 2) void conv3d_kernel(C3Args a) {
   __shared__ __attribute__((aligned(16))) __bf16 sH[3 * PE];
@@ -190,12 +181,7 @@ extern "C" {
 
 int aanet_conv3d_supported(int c, int co, int kd, int kh, int kw, int stride, int pad, int dil,
                            int groups) {
-  if (c <= 0 || co <= 0 || kd <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || dil <= 0 ||
-      groups <= 0)
-    return AANET_EINVAL;
-  const bool ok = kd == 3 && kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 &&
-                  groups == 1 && c3_channels(c) && c3_channels(co);
-  return ok ? AANET_OK : AANET_EUNSUPPORTED;
+  return c3_supported(1, 0, c, co, kd, kh, kw, stride, pad, 0, dil, groups);
 }
 
 size_t aanet_conv3d_pack_bytes(int co, int c) { return c3_pack_bytes(co, c); }
@@ -207,24 +193,8 @@ int aanet_conv3d_pack_f32(const float *w, int co, int c, void *wsplit, aanet_str
 int aanet_conv3d_fused_f32(const float *x, const void *wsplit, const float *bias,
                            const float *residual, int act, float *out, int n, int c, int d, int h,
                            int w, int co, aanet_stream_t stream) {
-  if (!x || !wsplit || !out || n <= 0 || c <= 0 || d <= 0 || h <= 0 || w <= 0 || co <= 0 ||
-      act < 0 || act > 2)
-    return AANET_EINVAL;
-  if (!c3_channels(c) || !c3_channels(co)) return AANET_EINVAL;
-  // per-image buffer resources with 32-bit offsets
-  if ((long)d * h * w * c * 4 >= (1L << 31) || (long)d * h * w * co * 4 >= (1L << 31))
-    return AANET_EUNSUPPORTED;
-  const long tiles = (long)host_div_up(w, TC) * host_div_up(h, TR) * n;
-  if (tiles > 0x7fffffffL) return AANET_EUNSUPPORTED;
-  C3Args a;
-  a.x = x;
-  a.wsplit = reinterpret_cast<const bf16x8 *>(wsplit);
-  a.bias = bias;
-  a.res = residual;
-  a.out = out;
-  a.N = n, a.C = c, a.D = d, a.H = h, a.W = w, a.Co = co, a.act = act;
-  hipLaunchKernelGGL(conv3d_kernel, dim3((unsigned)tiles, co / 32), dim3(NT), 0, as_hip(stream), a);
-  return aanet_launch_status();
+  return c3_launch(conv3d_kernel, C3Tiling{TR, TC, h, w}, C3Extent{d, h, w}, x, wsplit, bias,
+                   residual, act, out, n, c, d, h, w, co, stream);
 }
 
 }  // extern "C"

@@ -224,9 +224,7 @@ __global__ __launch_bounds__(NT) void conv3d_head_kernel(H3Args a) {
 
 int head_supported(bool up, int c, int co, int kd, int kh, int kw, int stride, int pad, int out_pad,
                    int dil, int groups) {
-  if (c <= 0 || co <= 0 || kd <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || out_pad < 0 ||
-      dil <= 0 || groups <= 0)
-    return AANET_EINVAL;
+  if (!c3_conv_args_ok(c, co, kd, kh, kw, stride, pad, out_pad, dil, groups)) return AANET_EINVAL;
   const bool ok = co == 1 && kd == 3 && kh == 3 && kw == 3 && stride == (up ? 2 : 1) && pad == 1 &&
                   out_pad == 0 && dil == 1 && groups == 1 && c3_channels(c);
   return ok ? AANET_OK : AANET_EUNSUPPORTED;
@@ -238,12 +236,10 @@ int head_launch(const float *x, const float *w, const float *bias, const float *
   if (!x || !w || !out || n <= 0 || c <= 0 || d <= 0 || h <= 0 || w_ <= 0 || act < 0 || act > 2)
     return AANET_EINVAL;
   if (!c3_channels(c)) return AANET_EINVAL;
-  // per-image buffer resources with 32-bit offsets
   const long dd = UP ? 2L * d - 1 : d, ho = UP ? 2L * h - 1 : h, wo = UP ? 2L * w_ - 1 : w_;
-  if ((long)d * h * w_ * c * 4 >= (1L << 31) || dd * ho * wo * 4 >= (1L << 31))
-    return AANET_EUNSUPPORTED;
-  const long tiles = (long)host_div_up(w_, TC) * host_div_up(h, TR) * n;
-  if (tiles > 0x7fffffffL) return AANET_EUNSUPPORTED;
+  if (!c3_volumes_ok((long)d * h * w_ * c, dd * ho * wo)) return AANET_EUNSUPPORTED;
+  const unsigned tiles = c3_tiles(h, w_, TR, TC, n);
+  if (!tiles) return AANET_EUNSUPPORTED;
   H3Args a;
   a.x = x;
   a.w = w;
@@ -251,7 +247,7 @@ int head_launch(const float *x, const float *w, const float *bias, const float *
   a.res = residual;
   a.out = out;
   a.N = n, a.D = d, a.H = h, a.W = w_, a.act = act;
-  const dim3 grid((unsigned)tiles), block(NT);
+  const dim3 grid(tiles), block(NT);
   switch (c) {
     case 32: hipLaunchKernelGGL((conv3d_head_kernel<2, UP>), grid, block, 0, as_hip(stream), a); break;
     case 64: hipLaunchKernelGGL((conv3d_head_kernel<4, UP>), grid, block, 0, as_hip(stream), a); break;

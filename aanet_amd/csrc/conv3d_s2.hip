@@ -29,7 +29,7 @@
 
 namespace {
 
-constexpr int NT = 256;                          // 4 waves: two tile rows x one 16-channel half each
+constexpr int NT = C3_NT;                        // 4 waves: two tile rows x one 16-channel half each
 constexpr int TR = 4, TC = 16;                   // output tile (ho x wo)
 constexpr int HR = 2 * TR + 1, HWW = 2 * TC + 1; // input halo 9 x 33
 constexpr int NEVEN = TC + 1;                    // even halo columns come first in a stored row
@@ -38,19 +38,10 @@ constexpr int PE = NPOS * 32;                    // bf16 per piece plane
 constexpr int HIT = (NPOS * 4 + NT - 1) / NT;    // halo octets (8 channels of a position) per thread
 constexpr unsigned OOB = C3_OOB;
 
-struct S2Args {
-  const float *x;        // [N][D][H][W][C]
-  const bf16x8 *wsplit;  // conv3d_common.h pack of [Co][C][3][3][3]
-  const float *bias;     // [Co] or NULL
-  const float *res;      // [N][Do][Ho][Wo][Co] or NULL
-  float *out;            // [N][Do][Ho][Wo][Co]
-  int N, C, D, H, W, Co, act;
-};
-
 // LDS position of halo (row, column): columns de-interleaved by parity
 __device__ __forceinline__ int s2_pos(int hr, int hc) { return hr * HWW + (hc & 1) * NEVEN + (hc >> 1); }
 
-__global__ __launch_bounds__(NT, 2) void conv3d_s2_kernel(S2Args a) {
+__global__ __launch_bounds__(NT, 2) void conv3d_s2_kernel(C3Args a) {
   __shared__ __attribute__((aligned(16))) __bf16 sH[3 * PE];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -190,42 +181,22 @@ extern "C" {
 
 int aanet_conv3d_s2_supported(int c, int co, int kd, int kh, int kw, int stride, int pad, int dil,
                               int groups) {
-  if (c <= 0 || co <= 0 || kd <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || dil <= 0 ||
-      groups <= 0)
-    return AANET_EINVAL;
-  const bool ok = kd == 3 && kh == 3 && kw == 3 && stride == 2 && pad == 1 && dil == 1 &&
-                  groups == 1 && c3_channels(c) && c3_channels(co);
-  return ok ? AANET_OK : AANET_EUNSUPPORTED;
+  return c3_supported(2, 0, c, co, kd, kh, kw, stride, pad, 0, dil, groups);
 }
 
-size_t aanet_conv3d_s2_pack_bytes(int co, int c) { return c3_pack_bytes(co, c); }
+// the pack is the stride-1 conv's
+size_t aanet_conv3d_s2_pack_bytes(int co, int c) { return aanet_conv3d_pack_bytes(co, c); }
 
 int aanet_conv3d_s2_pack_f32(const float *w, int co, int c, void *wsplit, aanet_stream_t stream) {
-  return c3_pack<false>(w, co, c, wsplit, stream);
+  return aanet_conv3d_pack_f32(w, co, c, wsplit, stream);
 }
 
 int aanet_conv3d_s2_fused_f32(const float *x, const void *wsplit, const float *bias,
                               const float *residual, int act, float *out, int n, int c, int d,
                               int h, int w, int co, aanet_stream_t stream) {
-  if (!x || !wsplit || !out || n <= 0 || c <= 0 || d <= 0 || h <= 0 || w <= 0 || co <= 0 ||
-      act < 0 || act > 2)
-    return AANET_EINVAL;
-  if (!c3_channels(c) || !c3_channels(co)) return AANET_EINVAL;
-  const long dout = (d + 1) / 2, ho = (h + 1) / 2, wo = (w + 1) / 2;
-  // per-image buffer resources with 32-bit offsets
-  if ((long)d * h * w * c * 4 >= (1L << 31) || dout * ho * wo * co * 4 >= (1L << 31))
-    return AANET_EUNSUPPORTED;
-  const long tiles = (long)host_div_up(wo, TC) * host_div_up(ho, TR) * n;
-  if (tiles > 0x7fffffffL) return AANET_EUNSUPPORTED;
-  S2Args a;
-  a.x = x;
-  a.wsplit = reinterpret_cast<const bf16x8 *>(wsplit);
-  a.bias = bias;
-  a.res = residual;
-  a.out = out;
-  a.N = n, a.C = c, a.D = d, a.H = h, a.W = w, a.Co = co, a.act = act;
-  hipLaunchKernelGGL(conv3d_s2_kernel, dim3((unsigned)tiles, co / 32), dim3(NT), 0, as_hip(stream), a);
-  return aanet_launch_status();
+  const C3Extent o{((long)d + 1) / 2, ((long)h + 1) / 2, ((long)w + 1) / 2};
+  return c3_launch(conv3d_s2_kernel, C3Tiling{TR, TC, o.h, o.w}, o, x, wsplit, bias, residual,
+                   act, out, n, c, d, h, w, co, stream);
 }
 
 }  // extern "C"

@@ -33,7 +33,7 @@
 
 namespace {
 
-constexpr int NT = 256;                     // 4 waves: two input rows x one 16-channel half each
+constexpr int NT = C3_NT;                   // 4 waves: two input rows x one 16-channel half each
 constexpr int TR = 4, TC = 16;              // input tile (h x w)
 constexpr int HR = TR + 1, HWW = TC + 1;    // halo 5 x 17
 constexpr int NPOS = HR * HWW;              // 85 positions
@@ -41,16 +41,7 @@ constexpr int PE = NPOS * 32;               // bf16 per piece plane
 constexpr int HIT = (NPOS * 4 + NT - 1) / NT;  // halo octets (8 channels of a position) per thread
 constexpr unsigned OOB = C3_OOB;
 
-struct D3Args {
-  const float *x;        // [N][D][H][W][C]
-  const bf16x8 *wsplit;  // conv3d_common.h pack of [C][Co][3][3][3]
-  const float *bias;     // [Co] or NULL
-  const float *res;      // [N][2D][2H][2W][Co] or NULL
-  float *out;            // [N][2D][2H][2W][Co]
-  int N, C, D, H, W, Co, act;
-};
-
-__global__ __launch_bounds__(NT, 2) void deconv3d2x_kernel(D3Args a) {
+__global__ __launch_bounds__(NT, 2) void deconv3d2x_kernel(C3Args a) {
   __shared__ __attribute__((aligned(16))) __bf16 sH[3 * PE];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -202,12 +193,7 @@ extern "C" {
 
 int aanet_deconv3d2x_supported(int c, int co, int kd, int kh, int kw, int stride, int pad,
                                int out_pad, int dil, int groups) {
-  if (c <= 0 || co <= 0 || kd <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || out_pad < 0 ||
-      dil <= 0 || groups <= 0)
-    return AANET_EINVAL;
-  const bool ok = kd == 3 && kh == 3 && kw == 3 && stride == 2 && pad == 1 && out_pad == 1 &&
-                  dil == 1 && groups == 1 && c3_channels(c) && c3_channels(co);
-  return ok ? AANET_OK : AANET_EUNSUPPORTED;
+  return c3_supported(2, 1, c, co, kd, kh, kw, stride, pad, out_pad, dil, groups);
 }
 
 size_t aanet_deconv3d2x_pack_bytes(int co, int c) { return c3_pack_bytes(co, c); }
@@ -219,24 +205,8 @@ int aanet_deconv3d2x_pack_f32(const float *w, int co, int c, void *wsplit, aanet
 int aanet_deconv3d2x_fused_f32(const float *x, const void *wsplit, const float *bias,
                                const float *residual, int act, float *out, int n, int c, int d,
                                int h, int w, int co, aanet_stream_t stream) {
-  if (!x || !wsplit || !out || n <= 0 || c <= 0 || d <= 0 || h <= 0 || w <= 0 || co <= 0 ||
-      act < 0 || act > 2)
-    return AANET_EINVAL;
-  if (!c3_channels(c) || !c3_channels(co)) return AANET_EINVAL;
-  // per-image buffer resources with 32-bit offsets
-  if ((long)d * h * w * c * 4 >= (1L << 31) || 8L * d * h * w * co * 4 >= (1L << 31))
-    return AANET_EUNSUPPORTED;
-  const long tiles = (long)host_div_up(w, TC) * host_div_up(h, TR) * n;
-  if (tiles > 0x7fffffffL) return AANET_EUNSUPPORTED;
-  D3Args a;
-  a.x = x;
-  a.wsplit = reinterpret_cast<const bf16x8 *>(wsplit);
-  a.bias = bias;
-  a.res = residual;
-  a.out = out;
-  a.N = n, a.C = c, a.D = d, a.H = h, a.W = w, a.Co = co, a.act = act;
-  hipLaunchKernelGGL(deconv3d2x_kernel, dim3((unsigned)tiles, co / 32), dim3(NT), 0, as_hip(stream), a);
-  return aanet_launch_status();
+  return c3_launch(deconv3d2x_kernel, C3Tiling{TR, TC, h, w}, C3Extent{2L * d, 2L * h, 2L * w}, x,
+                   wsplit, bias, residual, act, out, n, c, d, h, w, co, stream);
 }
 
 }  // extern "C"

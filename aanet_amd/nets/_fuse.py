@@ -40,8 +40,7 @@ def clear_fold_caches(module):
     writes through `.data` and HIP graph replays update a weight without bumping its _version."""
     for m in module.modules():
         for attr in ("_aanet_fold", "_aanet_fold_dense", "_aanet_affine", "_aanet_s2pack",
-                     "_aanet_s2pack_k", "_aanet_g3pack", "_aanet_fold3d", "_aanet_fold3d_s2",
-                     "_aanet_fold3d_up"):
+                     "_aanet_s2pack_k", "_aanet_g3pack", "_aanet_fold3d"):
             if attr in m.__dict__:
                 del m.__dict__[attr]
         for p in m.parameters(recurse=False):
@@ -87,10 +86,16 @@ def folded(conv, bn):
     return w, b, wp
 
 
-def folded3d(conv, bn):
-    """(bias, pre-split fragments) of a 3x3x3 Conv3d followed by eval BN (bn may be None) for
-    ops.conv3d_fused, cached on the conv module keyed by parameter versions like folded(); the
-    bias is None when neither the conv nor a BN has one."""
+# the packed 3-D kinds of ops.conv3d_kind: (pack, op) of ops, resolved at call time
+_PACKED3D = {"s1": ("pack_conv3d", "conv3d_fused"), "s2": ("pack_conv3d_s2", "conv3d_s2_fused"),
+             "up": ("pack_deconv3d2x", "deconv3d2x_fused")}
+
+
+def folded3d(kind, conv, bn):
+    """(bias, pre-split fragments) of a 3x3x3 conv of ops.conv3d_kind "s1", "s2" or "up" followed
+    by eval BN (bn may be None) for its op, cached on the conv module keyed by parameter versions
+    like folded(); the bias is None when neither the conv nor a BN has one.  The BN scale goes on
+    the weight's output-channel dimension: 1 for the transposed conv, else 0."""
     tensors = (conv.weight, conv.bias) + (_bn_tensors(bn) if bn is not None else ())
     key = _key(*tensors)
     cache = conv.__dict__.get("_aanet_fold3d")
@@ -102,55 +107,22 @@ def folded3d(conv, bn):
             b = None if conv.bias is None else conv.bias.contiguous()
         else:
             scale, shift = bn_scale_shift(bn)
-            w = conv.weight * scale.view(-1, 1, 1, 1, 1)
+            w = conv.weight * scale.view((1, -1, 1, 1, 1) if kind == "up" else (-1, 1, 1, 1, 1))
             b = (shift if conv.bias is None else conv.bias * scale + shift).contiguous()
-        wsplit = ops.pack_conv3d(w)
+        wsplit = getattr(ops, _PACKED3D[kind][0])(w)
     if wsplit is None:
-        raise ValueError("folded3d: a conv outside ops.conv3d_ok")
+        raise ValueError(f"folded3d: a conv outside ops.conv3d_kind {kind!r}")
     conv.__dict__["_aanet_fold3d"] = (key, b, wsplit)
     _lib.note_cache_fill()
     return b, wsplit
 
 
-def conv3d_bn_act(x, conv, bn=None, act=None, residual=None):
-    """act(BN(conv(x)) [+ residual]) of an ops.conv3d_ok Conv3d as ONE HIP kernel (BN folded into
-    the conv).  x and residual are channels_last_3d, and so is the result."""
-    b, wsplit = folded3d(conv, bn)
-    return ops.conv3d_fused(x, wsplit, b, conv.out_channels, act, residual)
-
-
-def folded3d_resample(conv, bn):
-    """folded3d for an ops.conv3d_s2_ok Conv3d (ops.conv3d_s2_fused) or an ops.deconv3d2x_ok
-    ConvTranspose3d (ops.deconv3d2x_fused), whose weight has its output channels in dimension 1."""
-    up = isinstance(conv, nn.ConvTranspose3d)
-    attr = "_aanet_fold3d_up" if up else "_aanet_fold3d_s2"
-    tensors = (conv.weight, conv.bias) + (_bn_tensors(bn) if bn is not None else ())
-    key = _key(*tensors)
-    cache = conv.__dict__.get(attr)
-    if cache is not None and cache[0] == key:
-        return cache[1], cache[2]
-    with torch.no_grad():
-        if bn is None:
-            w = conv.weight
-            b = None if conv.bias is None else conv.bias.contiguous()
-        else:
-            scale, shift = bn_scale_shift(bn)
-            w = conv.weight * (scale.view(1, -1, 1, 1, 1) if up else scale.view(-1, 1, 1, 1, 1))
-            b = (shift if conv.bias is None else conv.bias * scale + shift).contiguous()
-        wsplit = ops.pack_deconv3d2x(w) if up else ops.pack_conv3d_s2(w)
-    if wsplit is None:
-        raise ValueError("folded3d_resample: a conv outside ops.conv3d_s2_ok / ops.deconv3d2x_ok")
-    conv.__dict__[attr] = (key, b, wsplit)
-    _lib.note_cache_fill()
-    return b, wsplit
-
-
-def resample3d_bn_act(x, conv, bn=None, act=None, residual=None):
-    """conv3d_bn_act for an ops.conv3d_s2_ok Conv3d or an ops.deconv3d2x_ok ConvTranspose3d:
-    act(BN(conv(x)) [+ residual]) as ONE HIP kernel on channels_last_3d tensors."""
-    b, wsplit = folded3d_resample(conv, bn)
-    fn = ops.deconv3d2x_fused if isinstance(conv, nn.ConvTranspose3d) else ops.conv3d_s2_fused
-    return fn(x, wsplit, b, conv.out_channels, act, residual)
+def conv3d_bn_act(kind, x, conv, bn=None, act=None, residual=None):
+    """act(BN(conv(x)) [+ residual]) of a conv of ops.conv3d_kind "s1", "s2" or "up" as ONE HIP
+    kernel (BN folded into the conv).  x and residual are channels_last_3d, and so is the
+    result."""
+    b, wsplit = folded3d(kind, conv, bn)
+    return getattr(ops, _PACKED3D[kind][1])(x, wsplit, b, conv.out_channels, act, residual)
 
 
 def to_ndhwc(x):
@@ -200,20 +172,21 @@ def head3d_act(x, conv, act=None, residual=None):
 
 
 def run_fused_chain3d(mods, x, residual=None):
-    """Run a flat module list of a 3-D aggregator in eval: each ops.conv3d_ok (stride 1) or
-    ops.conv3d_s2_ok (stride 2) Conv3d or ops.deconv3d2x_ok ConvTranspose3d [+ BatchNorm3d]
+    """Run a flat module list of a 3-D aggregator in eval: each conv that ops.conv3d_kind places
+    on a packed kernel ("s1", "s2": Conv3d of stride 1 / 2; "up": ConvTranspose3d) [+ BatchNorm3d]
     [+ ReLU | LeakyReLU(0.2)] run of it is ONE HIP kernel on channels_last_3d tensors, and so is
-    each one-channel head (ops.conv3d_head_ok Conv3d, ops.deconv3d_head_ok ConvTranspose3d)
-    [+ ReLU | LeakyReLU(0.2)] with no BatchNorm3d behind it; anything else runs as is, on MIOpen.
+    each one-channel head ("head": Conv3d, "uphead": ConvTranspose3d) [+ ReLU | LeakyReLU(0.2)]
+    with no BatchNorm3d behind it; anything else runs as is, on MIOpen.
     residual: added to the LAST conv's BN output when that conv ends the list with no activation
     behind it (the `block(x) + x` adds of the aggregators)."""
     i, n = 0, len(mods)
     while i < n:
         m = mods[i]
-        s1 = ops.conv3d_ok(m)
-        head = not s1 and (ops.conv3d_head_ok(m) or ops.deconv3d_head_ok(m)) and \
-            not (i + 1 < n and isinstance(mods[i + 1], nn.BatchNorm3d))
-        if s1 or head or ops.conv3d_s2_ok(m) or ops.deconv3d2x_ok(m):
+        kind = ops.conv3d_kind(m)
+        head = kind in ("head", "uphead")
+        if head and i + 1 < n and isinstance(mods[i + 1], nn.BatchNorm3d):
+            kind = None  # the head kernels fold no BN
+        if kind is not None:
             bn = act = None
             j = i + 1
             if j < n and isinstance(mods[j], nn.BatchNorm3d):
@@ -226,7 +199,7 @@ def run_fused_chain3d(mods, x, residual=None):
             if head:
                 x = head3d_act(to_ndhwc(x), m, act, res)
             else:
-                x = (conv3d_bn_act if s1 else resample3d_bn_act)(to_ndhwc(x), m, bn, act, res)
+                x = conv3d_bn_act(kind, to_ndhwc(x), m, bn, act, res)
             i = j
         else:
             if isinstance(m, (nn.Conv3d, nn.ConvTranspose3d)) and not MIOPEN_NDHWC:

@@ -11,8 +11,10 @@ output channels runs on a HIP kernel on channels_last_3d tensors, with its Batch
 its activation -- and, where the graph has one, the residual add behind it -- in the epilogue:
 the stride-1 convs on csrc/conv3d.hip (ops.conv3d_fused), the stride-2 convs on csrc/conv3d_s2.hip
 (ops.conv3d_s2_fused) and the stride-2 transposed convs with output padding 1 on
-csrc/deconv3d.hip (ops.deconv3d2x_fused).  In the PSMNet hourglass conv5's `relu(. + pre)` and
-conv6's `+ cost0` of the enclosing aggregator are residuals of those launches; GC-Net's
+csrc/deconv3d.hip (ops.deconv3d2x_fused).  ops.conv3d_kind(module) names a module's kernel, and
+_fuse.run_fused_chain3d / _fuse.conv3d_bn_act(kind, ...) run it.  In the PSMNet hourglass
+conv5's `relu(. + pre)` and conv6's `+ cost0` of the enclosing aggregator are residuals of those
+launches; GC-Net's
 `x + skip` adds follow a ReLU and stay torch adds.  The one-channel heads -- StereoNet's and
 PSMNet-basic's final_conv, the hourglass aggregator's classif1-3[2] and GC-Net's trans_conv5
 (transposed, 32 -> 1, no output padding) -- run on csrc/conv3d_head.hip (ops.conv3d_head_fused /
@@ -164,15 +166,16 @@ class PSMNetHourglass(FoldCacheMixin, nn.Module):
             pre = _chain(self.conv1, x)
             res = None if postsqu is None else _fuse.to_ndhwc(postsqu)
             if ops.conv3d_ok(self.conv2[0]):  # relu(conv2(.) + postsqu) in one kernel
-                pre = _fuse.conv3d_bn_act(_fuse.to_ndhwc(pre), self.conv2[0], self.conv2[1], "relu", res)
+                pre = _fuse.conv3d_bn_act("s1", _fuse.to_ndhwc(pre), self.conv2[0], self.conv2[1],
+                                          "relu", res)
             else:
                 pre = self.conv2(_fuse.to_ncdhw(pre))
                 pre = F.relu(pre if postsqu is None else pre + postsqu, inplace=True)
             out = _chain(self.conv4, _chain(self.conv3, pre))
             skip = pre if presqu is None else presqu
             if ops.deconv3d2x_ok(self.conv5[0]):  # relu(conv5(.) + skip) in one kernel
-                post = _fuse.resample3d_bn_act(_fuse.to_ndhwc(out), self.conv5[0], self.conv5[1],
-                                               "relu", _fuse.to_ndhwc(skip))
+                post = _fuse.conv3d_bn_act("up", _fuse.to_ndhwc(out), self.conv5[0], self.conv5[1],
+                                           "relu", _fuse.to_ndhwc(skip))
             else:
                 post = F.relu(_chain(self.conv5, out) + skip, inplace=True)
             return _chain(self.conv6, post, residual=out_residual), pre, post

@@ -775,183 +775,91 @@ def conv3x3_grouped_nhwc(x, wsplit, bias, co, groups, dilation):
     return out
 
 
-# ------------------------------------------------------- 3-D aggregator convs (conv3d.hip) ------
-# Shapes that aanet_conv3d_supported takes but that lost to MIOpen in tools/conv3d_bench.py on the
-# MI355X: (c, co) pairs conv3d_ok refuses so they stay on MIOpen (DESIGN.md 7 names each).
+# ------------- 3-D aggregator convs (conv3d.hip, conv3d_s2.hip, deconv3d.hip, conv3d_head.hip) ------
+# Shapes the kernels take but that lost to MIOpen in tools/conv3d_bench.py on the MI355X, one set
+# per kind: (c, co) pairs, for the heads input channel counts c.  The *_ok functions refuse them
+# so they stay on MIOpen (DESIGN.md 7 names each); read at call time.
 CONV3D_SLOWER_THAN_MIOPEN = frozenset()
-
-
-def conv3d_supported(c, co, kernel=3, stride=1, padding=1, dilation=1, groups=1):
-    """Whether aanet_conv3d_fused_f32 takes a Conv3d of these parameters
-    (aanet_conv3d_supported): 3x3x3, stride 1, padding 1, dilation 1, one group, c and co in
-    {32, 64, 96, 128}."""
-    kd, kh, kw = (kernel,) * 3 if isinstance(kernel, int) else kernel
-    return _lib.lib().aanet_conv3d_supported(c, co, kd, kh, kw, stride, padding, dilation,
-                                             groups) == 0
-
-
-def conv3d_ok(conv):
-    """A conv module that conv3d_fused runs (aanet_conv3d_supported and the measured dispatch
-    table): nn.Conv3d or a subclass, zero padding, cubic parameters."""
-    if not isinstance(conv, torch.nn.Conv3d) or conv.padding_mode != "zeros" or \
-            isinstance(conv.padding, str):
-        return False
-    vals = []
-    for v in (conv.stride, conv.padding, conv.dilation):
-        if len(set(v)) != 1:
-            return False
-        vals.append(v[0])
-    c, co = conv.in_channels, conv.out_channels
-    return conv3d_supported(c, co, tuple(conv.kernel_size), *vals, conv.groups) and \
-        (c, co) not in CONV3D_SLOWER_THAN_MIOPEN
-
-
-def pack_conv3d(weight):
-    """Pre-split A fragments of a [co][c][3][3][3] weight for conv3d_fused (aanet_conv3d_pack_f32),
-    or None when the shape is outside the kernel."""
-    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
-        return None
-    if not weight.is_cuda:
-        raise NotImplementedError(
-            f"aanet_amd ops run only on the MI355X (HIP) device; weight is on {weight.device}")
-    co, c = weight.shape[:2]
-    nbytes = _lib.lib().aanet_conv3d_pack_bytes(co, c)
-    if not nbytes:
-        return None
-    out = torch.empty(nbytes // 2, device=weight.device, dtype=torch.int16)
-    w = weight.contiguous().float()
-    call("aanet_conv3d_pack_f32", ptr(w), co, c, ptr(out), stream_of(w))
-    return out
-
-
-def conv3d_fused(x, wsplit, bias, co, act=None, residual=None, out=None):
-    """act(conv3d(x, W) + bias [+ residual]) for a 3x3x3 stride-1 pad-1 conv with BN folded into
-    W / bias (aanet_conv3d_fused_f32; wsplit = pack_conv3d(W)).  x [N, C, D, H, W] and residual
-    [N, co, D, H, W] are channels_last_3d; so is the result (the caller's `out` when given)."""
-    for nm, t in (("x", x), ("wsplit", wsplit), ("bias", bias), ("residual", residual), ("out", out)):
-        if t is not None and not t.is_cuda:
-            raise NotImplementedError(
-                f"aanet_amd ops run only on the MI355X (HIP) device; {nm} is on {t.device}")
-    if x.dim() != 5:
-        raise ValueError("conv3d_fused: x must be [N, C, D, H, W]")
-    N, C, D, H, W = x.shape
-    shape = (N, co, D, H, W)
-    for nm, t, shp in (("x", x, tuple(x.shape)), ("residual", residual, shape), ("out", out, shape)):
-        if t is None:
-            continue
-        if t.dtype != torch.float32 or tuple(t.shape) != shp or not _lib.is_ndhwc(t) or \
-                t.device != x.device:
-            raise ValueError(f"conv3d_fused: {nm} must be a channels_last_3d float32 tensor of "
-                             f"shape {shp} on {x.device}")
-    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (co,) or
-                             not bias.is_contiguous()):
-        raise ValueError(f"conv3d_fused: bias must be a contiguous float32 tensor of shape ({co},)")
-    nbytes = _lib.lib().aanet_conv3d_pack_bytes(co, C)
-    if not nbytes or wsplit.numel() * wsplit.element_size() != nbytes:
-        raise ValueError(f"conv3d_fused: wsplit is not pack_conv3d of a [{co}][{C}][3][3][3] weight")
-    if out is None:
-        out = torch.empty(shape, device=x.device, dtype=x.dtype,
-                          memory_format=torch.channels_last_3d)
-    if x.numel() == 0:
-        return out
-    call("aanet_conv3d_fused_f32", ptr(x), ptr(wsplit), ptr(bias), ptr(residual), ACT[act],
-         ptr(out), N, C, D, H, W, co, stream_of(x))
-    return out
-
-
-# ------------------------- the hourglasses' down- / up-sampling convs (conv3d_s2.hip, deconv3d.hip)
-# (c, co) pairs the kernels take but that lost to MIOpen in tools/conv3d_bench.py on the MI355X;
-# conv3d_s2_ok / deconv3d2x_ok refuse them so they stay on MIOpen (DESIGN.md 7 names each).
 CONV3D_S2_SLOWER_THAN_MIOPEN = frozenset()
 DECONV3D2X_SLOWER_THAN_MIOPEN = frozenset()
+CONV3D_HEAD_SLOWER_THAN_MIOPEN = frozenset()
+DECONV3D_HEAD_SLOWER_THAN_MIOPEN = frozenset()
+
+_Kind3d = collections.namedtuple("_Kind3d", "stem module cubic osize co_dim slower")
+_CONV_CUBIC = ("stride", "padding", "dilation")
+_DECONV_CUBIC = ("stride", "padding", "output_padding", "dilation")
+# The five kinds: C symbol stem (aanet_<stem>_*), module class, the per-axis parameters in the
+# order the support query takes them, output extent of an input extent, the weight dimension
+# that holds co, and the name of the dispatch set above.  A head has one output channel.
+_KINDS3D = {
+    "s1": _Kind3d("conv3d", torch.nn.Conv3d, _CONV_CUBIC, lambda v: v, 0,
+                  "CONV3D_SLOWER_THAN_MIOPEN"),
+    "s2": _Kind3d("conv3d_s2", torch.nn.Conv3d, _CONV_CUBIC, lambda v: (v + 1) // 2, 0,
+                  "CONV3D_S2_SLOWER_THAN_MIOPEN"),
+    "up": _Kind3d("deconv3d2x", torch.nn.ConvTranspose3d, _DECONV_CUBIC, lambda v: 2 * v, 1,
+                  "DECONV3D2X_SLOWER_THAN_MIOPEN"),
+    "head": _Kind3d("conv3d_head", torch.nn.Conv3d, _CONV_CUBIC, lambda v: v, 0,
+                    "CONV3D_HEAD_SLOWER_THAN_MIOPEN"),
+    "uphead": _Kind3d("deconv3d_head", torch.nn.ConvTranspose3d, _DECONV_CUBIC,
+                      lambda v: 2 * v - 1, 1, "DECONV3D_HEAD_SLOWER_THAN_MIOPEN"),
+}
+_HEADS3D = ("head", "uphead")
 
 
-def conv3d_s2_supported(c, co, kernel=3, stride=2, padding=1, dilation=1, groups=1):
-    """Whether aanet_conv3d_s2_fused_f32 takes a Conv3d of these parameters
-    (aanet_conv3d_s2_supported): 3x3x3, stride 2, padding 1, dilation 1, one group, c and co in
-    {32, 64, 96, 128}."""
+def _supported(kind, c, co, kernel, *params):
+    """The C support query of a kind; params: its cubic parameters, then the groups."""
     kd, kh, kw = (kernel,) * 3 if isinstance(kernel, int) else kernel
-    return _lib.lib().aanet_conv3d_s2_supported(c, co, kd, kh, kw, stride, padding, dilation,
-                                                groups) == 0
+    query = getattr(_lib.lib(), f"aanet_{_KINDS3D[kind].stem}_supported")
+    return query(c, co, kd, kh, kw, *params) == 0
 
 
-def deconv3d2x_supported(c, co, kernel=3, stride=2, padding=1, output_padding=1, dilation=1,
-                         groups=1):
-    """Whether aanet_deconv3d2x_fused_f32 takes a ConvTranspose3d of these parameters
-    (aanet_deconv3d2x_supported): 3x3x3, stride 2, padding 1, output padding 1, dilation 1, one
-    group, c and co in {32, 64, 96, 128}."""
-    kd, kh, kw = (kernel,) * 3 if isinstance(kernel, int) else kernel
-    return _lib.lib().aanet_deconv3d2x_supported(c, co, kd, kh, kw, stride, padding,
-                                                 output_padding, dilation, groups) == 0
-
-
-def _cubic(conv, names):
-    """The common value of each of conv's per-axis parameters, or None when one is not cubic."""
-    vals = []
-    for nm in names:
-        v = getattr(conv, nm)
-        if len(set(v)) != 1:
-            return None
-        vals.append(v[0])
-    return vals
-
-
-def conv3d_s2_ok(conv):
-    """A conv module that conv3d_s2_fused runs (aanet_conv3d_s2_supported and the measured
-    dispatch table): nn.Conv3d or a subclass, zero padding, cubic parameters."""
-    if not isinstance(conv, torch.nn.Conv3d) or conv.padding_mode != "zeros" or \
+def _module_ok(kind, conv):
+    """Whether conv is a module of this kind that its op runs: the module class or a subclass,
+    zero padding, cubic parameters the C query takes, and not in the kind's dispatch set."""
+    k = _KINDS3D[kind]
+    if not isinstance(conv, k.module) or conv.padding_mode != "zeros" or \
             isinstance(conv.padding, str):
         return False
-    vals = _cubic(conv, ("stride", "padding", "dilation"))
-    c, co = conv.in_channels, conv.out_channels
-    return vals is not None and \
-        conv3d_s2_supported(c, co, tuple(conv.kernel_size), *vals, conv.groups) and \
-        (c, co) not in CONV3D_S2_SLOWER_THAN_MIOPEN
-
-
-def deconv3d2x_ok(conv):
-    """A transposed conv module that deconv3d2x_fused runs (aanet_deconv3d2x_supported and the
-    measured dispatch table): nn.ConvTranspose3d or a subclass, cubic parameters."""
-    if not isinstance(conv, torch.nn.ConvTranspose3d) or conv.padding_mode != "zeros":
+    vals = [getattr(conv, nm) for nm in k.cubic]
+    if any(len(set(v)) != 1 for v in vals):
         return False
-    vals = _cubic(conv, ("stride", "padding", "output_padding", "dilation"))
     c, co = conv.in_channels, conv.out_channels
-    return vals is not None and \
-        deconv3d2x_supported(c, co, tuple(conv.kernel_size), *vals, conv.groups) and \
-        (c, co) not in DECONV3D2X_SLOWER_THAN_MIOPEN
+    return _supported(kind, c, co, tuple(conv.kernel_size), *(v[0] for v in vals), conv.groups) \
+        and (c if kind in _HEADS3D else (c, co)) not in globals()[k.slower]
 
 
-def _pack3d(stem, weight, co, c):
+def conv3d_kind(module):
+    """Which of the five 3-D kernels runs this module: "s1" (ops.conv3d_fused), "s2"
+    (conv3d_s2_fused), "up" (deconv3d2x_fused), "head" (conv3d_head_fused) or "uphead"
+    (deconv3d_head_fused); None for anything else, which stays on MIOpen."""
+    for kind in _KINDS3D:
+        if _module_ok(kind, module):
+            return kind
+    return None
+
+
+def _pack3d(kind, weight):
+    """Pre-split A fragments of a 3x3x3 weight for a packed kind, or None outside its kernel."""
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
+        return None
     if not weight.is_cuda:
         raise NotImplementedError(
             f"aanet_amd ops run only on the MI355X (HIP) device; weight is on {weight.device}")
-    nbytes = getattr(_lib.lib(), f"aanet_{stem}_pack_bytes")(co, c)
+    k = _KINDS3D[kind]
+    co, c = weight.shape[k.co_dim], weight.shape[1 - k.co_dim]
+    nbytes = getattr(_lib.lib(), f"aanet_{k.stem}_pack_bytes")(co, c)
     if not nbytes:
         return None
     out = torch.empty(nbytes // 2, device=weight.device, dtype=torch.int16)
     w = weight.contiguous().float()
-    call(f"aanet_{stem}_pack_f32", ptr(w), co, c, ptr(out), stream_of(w))
+    call(f"aanet_{k.stem}_pack_f32", ptr(w), co, c, ptr(out), stream_of(w))
     return out
 
 
-def pack_conv3d_s2(weight):
-    """Pre-split A fragments of a [co][c][3][3][3] Conv3d weight for conv3d_s2_fused
-    (aanet_conv3d_s2_pack_f32), or None when the shape is outside the kernel."""
-    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
-        return None
-    return _pack3d("conv3d_s2", weight, weight.shape[0], weight.shape[1])
-
-
-def pack_deconv3d2x(weight):
-    """Pre-split A fragments of a [c][co][3][3][3] ConvTranspose3d weight for deconv3d2x_fused
-    (aanet_deconv3d2x_pack_f32), or None when the shape is outside the kernel."""
-    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
-        return None
-    return _pack3d("deconv3d2x", weight, weight.shape[1], weight.shape[0])
-
-
-def _resample3d_fused(name, stem, packer, osize, x, wsplit, bias, co, act, residual, out):
-    """conv3d_fused's checks and launch for a kernel whose output is osize(d, h, w)."""
+def _conv3d_launch(kind, x, wsplit, bias, co, act, residual, out):
+    """The checks and the launch of the three packed ops."""
+    k = _KINDS3D[kind]
+    name = f"{k.stem}_fused"
     for nm, t in (("x", x), ("wsplit", wsplit), ("bias", bias), ("residual", residual), ("out", out)):
         if t is not None and not t.is_cuda:
             raise NotImplementedError(
@@ -959,7 +867,7 @@ def _resample3d_fused(name, stem, packer, osize, x, wsplit, bias, co, act, resid
     if x.dim() != 5:
         raise ValueError(f"{name}: x must be [N, C, D, H, W]")
     N, C, D, H, W = x.shape
-    shape = (N, co) + tuple(osize(v) for v in (D, H, W))
+    shape = (N, co) + tuple(k.osize(v) for v in (D, H, W))
     for nm, t, shp in (("x", x, tuple(x.shape)), ("residual", residual, shape), ("out", out, shape)):
         if t is None:
             continue
@@ -970,18 +878,85 @@ def _resample3d_fused(name, stem, packer, osize, x, wsplit, bias, co, act, resid
     if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (co,) or
                              not bias.is_contiguous()):
         raise ValueError(f"{name}: bias must be a contiguous float32 tensor of shape ({co},)")
-    nbytes = getattr(_lib.lib(), f"aanet_{stem}_pack_bytes")(co, C)
+    nbytes = getattr(_lib.lib(), f"aanet_{k.stem}_pack_bytes")(co, C)
     if not nbytes or wsplit.numel() * wsplit.element_size() != nbytes:
-        raise ValueError(f"{name}: wsplit is not {packer} of a 3x3x3 weight with {C} input and "
-                         f"{co} output channels")
+        weight = f"[{co}][{C}][3][3][3] weight" if kind == "s1" else \
+            f"3x3x3 weight with {C} input and {co} output channels"
+        raise ValueError(f"{name}: wsplit is not pack_{k.stem} of a {weight}")
     if out is None:
         out = torch.empty(shape, device=x.device, dtype=x.dtype,
                           memory_format=torch.channels_last_3d)
     if x.numel() == 0:
         return out
-    call(f"aanet_{stem}_fused_f32", ptr(x), ptr(wsplit), ptr(bias), ptr(residual), ACT[act],
+    call(f"aanet_{k.stem}_fused_f32", ptr(x), ptr(wsplit), ptr(bias), ptr(residual), ACT[act],
          ptr(out), N, C, D, H, W, co, stream_of(x))
     return out
+
+
+def conv3d_supported(c, co, kernel=3, stride=1, padding=1, dilation=1, groups=1):
+    """Whether aanet_conv3d_fused_f32 takes a Conv3d of these parameters
+    (aanet_conv3d_supported): 3x3x3, stride 1, padding 1, dilation 1, one group, c and co in
+    {32, 64, 96, 128}."""
+    return _supported("s1", c, co, kernel, stride, padding, dilation, groups)
+
+
+def conv3d_ok(conv):
+    """A conv module that conv3d_fused runs (aanet_conv3d_supported and the measured dispatch
+    table): nn.Conv3d or a subclass, zero padding, cubic parameters."""
+    return _module_ok("s1", conv)
+
+
+def pack_conv3d(weight):
+    """Pre-split A fragments of a [co][c][3][3][3] weight for conv3d_fused (aanet_conv3d_pack_f32),
+    or None when the shape is outside the kernel."""
+    return _pack3d("s1", weight)
+
+
+def conv3d_fused(x, wsplit, bias, co, act=None, residual=None, out=None):
+    """act(conv3d(x, W) + bias [+ residual]) for a 3x3x3 stride-1 pad-1 conv with BN folded into
+    W / bias (aanet_conv3d_fused_f32; wsplit = pack_conv3d(W)).  x [N, C, D, H, W] and residual
+    [N, co, D, H, W] are channels_last_3d; so is the result (the caller's `out` when given)."""
+    return _conv3d_launch("s1", x, wsplit, bias, co, act, residual, out)
+
+
+# the hourglasses' down- / up-sampling convs (conv3d_s2.hip, deconv3d.hip)
+def conv3d_s2_supported(c, co, kernel=3, stride=2, padding=1, dilation=1, groups=1):
+    """Whether aanet_conv3d_s2_fused_f32 takes a Conv3d of these parameters
+    (aanet_conv3d_s2_supported): 3x3x3, stride 2, padding 1, dilation 1, one group, c and co in
+    {32, 64, 96, 128}."""
+    return _supported("s2", c, co, kernel, stride, padding, dilation, groups)
+
+
+def deconv3d2x_supported(c, co, kernel=3, stride=2, padding=1, output_padding=1, dilation=1,
+                         groups=1):
+    """Whether aanet_deconv3d2x_fused_f32 takes a ConvTranspose3d of these parameters
+    (aanet_deconv3d2x_supported): 3x3x3, stride 2, padding 1, output padding 1, dilation 1, one
+    group, c and co in {32, 64, 96, 128}."""
+    return _supported("up", c, co, kernel, stride, padding, output_padding, dilation, groups)
+
+
+def conv3d_s2_ok(conv):
+    """A conv module that conv3d_s2_fused runs (aanet_conv3d_s2_supported and the measured
+    dispatch table): nn.Conv3d or a subclass, zero padding, cubic parameters."""
+    return _module_ok("s2", conv)
+
+
+def deconv3d2x_ok(conv):
+    """A transposed conv module that deconv3d2x_fused runs (aanet_deconv3d2x_supported and the
+    measured dispatch table): nn.ConvTranspose3d or a subclass, cubic parameters."""
+    return _module_ok("up", conv)
+
+
+def pack_conv3d_s2(weight):
+    """Pre-split A fragments of a [co][c][3][3][3] Conv3d weight for conv3d_s2_fused
+    (aanet_conv3d_s2_pack_f32), or None when the shape is outside the kernel."""
+    return _pack3d("s2", weight)
+
+
+def pack_deconv3d2x(weight):
+    """Pre-split A fragments of a [c][co][3][3][3] ConvTranspose3d weight for deconv3d2x_fused
+    (aanet_deconv3d2x_pack_f32), or None when the shape is outside the kernel."""
+    return _pack3d("up", weight)
 
 
 def conv3d_s2_fused(x, wsplit, bias, co, act=None, residual=None, out=None):
@@ -989,8 +964,7 @@ def conv3d_s2_fused(x, wsplit, bias, co, act=None, residual=None, out=None):
     into W / bias (aanet_conv3d_s2_fused_f32; wsplit = pack_conv3d_s2(W)).  x [N, C, D, H, W] and
     residual [N, co, (D+1)//2, (H+1)//2, (W+1)//2] are channels_last_3d; so is the result (the
     caller's `out` when given)."""
-    return _resample3d_fused("conv3d_s2_fused", "conv3d_s2", "pack_conv3d_s2",
-                             lambda v: (v + 1) // 2, x, wsplit, bias, co, act, residual, out)
+    return _conv3d_launch("s2", x, wsplit, bias, co, act, residual, out)
 
 
 def deconv3d2x_fused(x, wsplit, bias, co, act=None, residual=None, out=None):
@@ -998,24 +972,15 @@ def deconv3d2x_fused(x, wsplit, bias, co, act=None, residual=None, out=None):
     a 3x3x3 transposed conv with BN folded into W / bias (aanet_deconv3d2x_fused_f32; wsplit =
     pack_deconv3d2x(W)).  x [N, C, D, H, W] and residual [N, co, 2D, 2H, 2W] are
     channels_last_3d; so is the result (the caller's `out` when given)."""
-    return _resample3d_fused("deconv3d2x_fused", "deconv3d2x", "pack_deconv3d2x",
-                             lambda v: 2 * v, x, wsplit, bias, co, act, residual, out)
+    return _conv3d_launch("up", x, wsplit, bias, co, act, residual, out)
 
 
-# ------------------------------------- the aggregators' one-channel heads (conv3d_head.hip) ------
-# Input channel counts c the head kernels take but that lost to MIOpen in tools/conv3d_bench.py on
-# the MI355X; conv3d_head_ok / deconv3d_head_ok refuse them so they stay on MIOpen (DESIGN.md 7).
-CONV3D_HEAD_SLOWER_THAN_MIOPEN = frozenset()
-DECONV3D_HEAD_SLOWER_THAN_MIOPEN = frozenset()
-
-
+# the aggregators' one-channel heads (conv3d_head.hip)
 def conv3d_head_supported(c, co=1, kernel=3, stride=1, padding=1, dilation=1, groups=1):
     """Whether aanet_conv3d_head_f32 takes a Conv3d of these parameters
     (aanet_conv3d_head_supported): one output channel, 3x3x3, stride 1, padding 1, dilation 1, one
     group, c in {32, 64, 96, 128}."""
-    kd, kh, kw = (kernel,) * 3 if isinstance(kernel, int) else kernel
-    return _lib.lib().aanet_conv3d_head_supported(c, co, kd, kh, kw, stride, padding, dilation,
-                                                  groups) == 0
+    return _supported("head", c, co, kernel, stride, padding, dilation, groups)
 
 
 def deconv3d_head_supported(c, co=1, kernel=3, stride=2, padding=1, output_padding=0, dilation=1,
@@ -1023,38 +988,25 @@ def deconv3d_head_supported(c, co=1, kernel=3, stride=2, padding=1, output_paddi
     """Whether aanet_deconv3d_head_f32 takes a ConvTranspose3d of these parameters
     (aanet_deconv3d_head_supported): one output channel, 3x3x3, stride 2, padding 1, output
     padding 0, dilation 1, one group, c in {32, 64, 96, 128}."""
-    kd, kh, kw = (kernel,) * 3 if isinstance(kernel, int) else kernel
-    return _lib.lib().aanet_deconv3d_head_supported(c, co, kd, kh, kw, stride, padding,
-                                                    output_padding, dilation, groups) == 0
+    return _supported("uphead", c, co, kernel, stride, padding, output_padding, dilation, groups)
 
 
 def conv3d_head_ok(conv):
     """A conv module that conv3d_head_fused runs (aanet_conv3d_head_supported and the measured
     dispatch table): nn.Conv3d or a subclass, zero padding, cubic parameters."""
-    if not isinstance(conv, torch.nn.Conv3d) or conv.padding_mode != "zeros" or \
-            isinstance(conv.padding, str):
-        return False
-    vals = _cubic(conv, ("stride", "padding", "dilation"))
-    c, co = conv.in_channels, conv.out_channels
-    return vals is not None and \
-        conv3d_head_supported(c, co, tuple(conv.kernel_size), *vals, conv.groups) and \
-        c not in CONV3D_HEAD_SLOWER_THAN_MIOPEN
+    return _module_ok("head", conv)
 
 
 def deconv3d_head_ok(conv):
     """A transposed conv module that deconv3d_head_fused runs (aanet_deconv3d_head_supported and
     the measured dispatch table): nn.ConvTranspose3d or a subclass, cubic parameters."""
-    if not isinstance(conv, torch.nn.ConvTranspose3d) or conv.padding_mode != "zeros":
-        return False
-    vals = _cubic(conv, ("stride", "padding", "output_padding", "dilation"))
-    c, co = conv.in_channels, conv.out_channels
-    return vals is not None and \
-        deconv3d_head_supported(c, co, tuple(conv.kernel_size), *vals, conv.groups) and \
-        c not in DECONV3D_HEAD_SLOWER_THAN_MIOPEN
+    return _module_ok("uphead", conv)
 
 
-def _head3d_fused(name, up, x, weight, bias, act, residual, out):
-    """The checks and the launch of the two head ops; up: the transposed head."""
+def _head3d_launch(kind, x, weight, bias, act, residual, out):
+    """The checks and the launch of the two head ops."""
+    k = _KINDS3D[kind]
+    name = f"{k.stem}_fused"
     for nm, t in (("x", x), ("weight", weight), ("bias", bias), ("residual", residual), ("out", out)):
         if t is not None and not t.is_cuda:
             raise NotImplementedError(
@@ -1064,14 +1016,14 @@ def _head3d_fused(name, up, x, weight, bias, act, residual, out):
     N, C, D, H, W = x.shape
     if x.dtype != torch.float32 or not _lib.is_ndhwc(x):
         raise ValueError(f"{name}: x must be a channels_last_3d float32 tensor")
-    wshape = (C, 1, 3, 3, 3) if up else (1, C, 3, 3, 3)
+    wshape = tuple(1 if i == k.co_dim else C for i in (0, 1)) + (3, 3, 3)
     if weight.dtype != torch.float32 or tuple(weight.shape) != wshape or \
             not weight.is_contiguous() or weight.device != x.device:
         raise ValueError(f"{name}: weight must be a contiguous float32 tensor of shape {wshape} "
                          f"on {x.device}")
-    if not (deconv3d_head_supported if up else conv3d_head_supported)(C):
+    if not globals()[f"{k.stem}_supported"](C):  # the kind's public query, at its defaults
         raise ValueError(f"{name}: {C} input channels are outside the kernel (32, 64, 96, 128)")
-    shape = (N, 1) + tuple(2 * v - 1 if up else v for v in (D, H, W))
+    shape = (N, 1) + tuple(k.osize(v) for v in (D, H, W))
     for nm, t in (("residual", residual), ("out", out)):
         if t is None:
             continue
@@ -1086,8 +1038,8 @@ def _head3d_fused(name, up, x, weight, bias, act, residual, out):
         out = torch.empty(shape, device=x.device, dtype=x.dtype)
     if x.numel() == 0:
         return out
-    call("aanet_deconv3d_head_f32" if up else "aanet_conv3d_head_f32", ptr(x), ptr(weight),
-         ptr(bias), ptr(residual), ACT[act], ptr(out), N, C, D, H, W, stream_of(x))
+    call(f"aanet_{k.stem}_f32", ptr(x), ptr(weight), ptr(bias), ptr(residual), ACT[act], ptr(out),
+         N, C, D, H, W, stream_of(x))
     return out
 
 
@@ -1096,7 +1048,7 @@ def conv3d_head_fused(x, weight, bias, act=None, residual=None, out=None):
     3x3x3 conv (aanet_conv3d_head_f32).  x [N, C, D, H, W] is channels_last_3d float32; weight is
     the module's own contiguous [1, C, 3, 3, 3] (no pack); bias is a (1,) tensor or None; residual
     and the result (the caller's `out` when given) are contiguous [N, 1, D, H, W]."""
-    return _head3d_fused("conv3d_head_fused", False, x, weight, bias, act, residual, out)
+    return _head3d_launch("head", x, weight, bias, act, residual, out)
 
 
 def deconv3d_head_fused(x, weight, bias, act=None, residual=None, out=None):
@@ -1104,7 +1056,7 @@ def deconv3d_head_fused(x, weight, bias, act=None, residual=None, out=None):
     for a one-output-channel 3x3x3 transposed conv (aanet_deconv3d_head_f32).  x [N, C, D, H, W]
     is channels_last_3d float32; weight is the module's own contiguous [C, 1, 3, 3, 3]; residual
     and the result (the caller's `out` when given) are contiguous [N, 1, 2D-1, 2H-1, 2W-1]."""
-    return _head3d_fused("deconv3d_head_fused", True, x, weight, bias, act, residual, out)
+    return _head3d_launch("uphead", x, weight, bias, act, residual, out)
 
 
 def csa_sum(inputs, act="leaky"):
