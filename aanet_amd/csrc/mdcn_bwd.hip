@@ -251,7 +251,10 @@ __global__ __launch_bounds__(NT) void mdcn_bwd_data_nhwc_kernel(MdcnArgs a, cons
       qq[2] = __builtin_bit_cast(float, on && (s.ok & 4) ? s.i3 : -1);
       qq[3] = __builtin_bit_cast(float, on && (s.ok & 8) ? s.i4 : -1);
       qq[4] = hh * hw, qq[5] = hh * s.lw, qq[6] = s.lh * hw, qq[7] = s.lh * s.lw;
-      qq[8] = s.m, qq[9] = s.lh, qq[10] = s.lw, qq[11] = on ? 1.f : 0.f;
+      // an invalid sample's fractions are 0, not h - (float)(int)h (inf or NaN for an offset of
+      // +-inf or +-3e38): its corners read as 0, and 0 * inf would put NaN where the reference
+      // has grad_offset = grad_mask = 0 (kernel.cu:716-721)
+      qq[8] = s.m, qq[9] = on ? s.lh : 0.f, qq[10] = on ? s.lw : 0.f, qq[11] = on ? 1.f : 0.f;
     }
     float gm[2] = {0.f, 0.f}, goh[2] = {0.f, 0.f}, gow[2] = {0.f, 0.f};
     for (int c0 = g * cpg; c0 < (g + 1) * cpg; c0 += KC) {
@@ -484,14 +487,17 @@ __global__ __launch_bounds__(NT, 2) void mdcn_bwd_data_win_kernel(MdcnArgs a, co
         make_samp(s, (float)(sy * a.stride - a.pad + i * a.dil) + roh,
                   (float)(sx * a.stride - a.pad + j * a.dil) + row, a.H, a.W, m);
         const bool on = pvalid && s.valid;
-        const float hh = 1.f - s.lh, hw = 1.f - s.lw;
         float *qq = sS + lane * 16;
         qq[0] = __builtin_bit_cast(float, on && (s.ok & 1) ? s.i1 : -1);
         qq[1] = __builtin_bit_cast(float, on && (s.ok & 2) ? s.i2 : -1);
         qq[2] = __builtin_bit_cast(float, on && (s.ok & 4) ? s.i3 : -1);
         qq[3] = __builtin_bit_cast(float, on && (s.ok & 8) ? s.i4 : -1);
-        qq[4] = hh * hw, qq[5] = hh * s.lw, qq[6] = s.lh * hw, qq[7] = s.lh * s.lw;
-        qq[8] = s.m, qq[9] = s.lh, qq[10] = s.lw, qq[11] = on ? 1.f : 0.f;
+        // make_samp's own weights (0 for a corner outside the image, the same products else) and
+        // fractions 0 for an invalid sample: h - (float)(int)h is inf or NaN for an offset of +-inf
+        // or +-3e38, and 0 * inf would put NaN into the sampled columns (grad_weight) and where
+        // the reference has grad_offset = grad_mask = 0 (kernel.cu:716-721)
+        qq[4] = s.w1, qq[5] = s.w2, qq[6] = s.w3, qq[7] = s.w4;
+        qq[8] = s.m, qq[9] = on ? s.lh : 0.f, qq[10] = on ? s.lw : 0.f, qq[11] = on ? 1.f : 0.f;
         // window position of the 2x2 corner block (top-left), or -1: global atomics
         int wpos = -1;
         if (on) {

@@ -33,8 +33,12 @@ __device__ __forceinline__ WarpCoord make_coord(float ix, float iy) {
   c.ix = ix;
   c.iy = iy;
   const float fx = floorf(ix), fy = floorf(iy);
-  c.x0 = (int)fx;
-  c.y0 = (int)fy;
+  // the corner indices of a position far outside (|disp| up to inf): clamped to [-2, 2^30] before
+  // the conversion, where both x0 and x0 + 1 are still outside any image.  Unclamped, (int)inf is
+  // INT_MAX and x0 + 1 overflows: the compiler's bound checks of that corner then pass, and its
+  // NaN weight (inf - inf) reached the validity mask.
+  c.x0 = (int)fminf(fmaxf(fx, -2.f), 1073741824.f);
+  c.y0 = (int)fminf(fmaxf(fy, -2.f), 1073741824.f);
   const float x1 = fx + 1.f, y1 = fy + 1.f;
   c.wnw = (x1 - ix) * (y1 - iy);
   c.wne = (ix - fx) * (y1 - iy);

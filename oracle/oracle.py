@@ -238,7 +238,8 @@ def disp_warp(img, disp):
         out += np.moveaxis(v * (ww * ok)[..., None], -1, 1)
     m = np.zeros(ix.shape, np.float32)
     for yy, xx, ww in _corners(ix, iy):  # grid_sample(ones, zeros padding): unclipped
-        m += ww * ((yy >= 0) & (yy < H) & (xx >= 0) & (xx < W))
+        # (a corner outside the image adds 0 whatever its weight: NaN at an infinite position)
+        m += np.where((yy >= 0) & (yy < H) & (xx >= 0) & (xx < W), ww, np.float32(0))
     valid = np.where(m < np.float32(0.9999), np.float32(0), np.float32(1))
     return out, np.repeat(valid[:, None], C, axis=1)
 
