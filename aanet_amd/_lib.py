@@ -44,6 +44,9 @@ _SIGNATURES = {
     "aanet_conv2d_wgrad_f32": [_P] * 4 + [_I] * 12 + [_P, ctypes.c_size_t, _P],
     "aanet_resize_bilinear_bwd_f32": [_P, _P, _L] + [_I] * 4 + [_P],
     "aanet_resize_bilinear_f32": [_P, _P, _L] + [_I] * 4 + [_P],
+    "aanet_disp_loss_f32": [_I] + [_P] * 8 + [_I] * 3 + [_P] * 6 + [ctypes.c_size_t, _P],
+    "aanet_disp_loss_bwd_f32": [_I] + [_P] * 9 + [_I] * 3 + [_P] * 4,
+    "aanet_disp_metrics_f32": [_P, _I, _I, _P, _P] + [_I] * 4 + [_P] * 4 + [ctypes.c_size_t, _P],
     "aanet_deconv2x_assemble_f32": [_P, _P, _P] + [_I] * 5 + [_P],
     "aanet_deconv2x_assemble_nhwc_f32": [_P, _P, _P] + [_I] * 5 + [_P],
     "aanet_concat_nhwc_f32": [_P, _P, _P] + [_I] * 5 + [_P],
@@ -85,6 +88,8 @@ _SIZE_FUNCTIONS = [
     ("aanet_mdcn_bwd_det_workspace_size", [_I] * 12, ctypes.c_size_t),
     ("aanet_mdcn_bwd_ws_workspace_size", [_I] * 12, ctypes.c_size_t),
     ("aanet_conv2d_wgrad_workspace_size", [_I] * 11, ctypes.c_size_t),
+    ("aanet_disp_loss_workspace_size", [_I] * 4, ctypes.c_size_t),
+    ("aanet_disp_metrics_workspace_size", [_I] * 3, ctypes.c_size_t),
     ("aanet_conv_weight_pack_split_bytes", [_I] * 5, _L),
     ("aanet_conv3x3s2_pack_bytes", [_I, _I], ctypes.c_size_t),
     ("aanet_conv3x3_grouped_pack_bytes", [_I, _I, _I], ctypes.c_size_t),

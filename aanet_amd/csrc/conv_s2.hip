@@ -111,7 +111,7 @@ __device__ __forceinline__ void s2_epilogue(const S2Args &a, const f32x4 (&acc)[
                                                       (short)0, cb * P * 4, 0x00020000);
   const int lo = (4 * kr * P + pix) * 4;  // channel 4kr's plane + this pixel
   // the resize stencil of this pixel (PyTorch upsample_bilinear2d, align_corners=False, as in
-  // csa.hip's bilinear_resize): the same four offsets and weights for every channel plane
+  // resize.h's bilinear_resize): the same four offsets and weights for every channel plane
   int lu[4] = {0, 0, 0, 0};
   float h0l = 0.f, h1l = 0.f, w0l = 0.f, w1l = 0.f;
   if (hup) {

@@ -5,6 +5,7 @@
 // One pass: each output element reads its same-size term once and 4 taps of each resized term,
 // instead of the reference's separate interpolate / add / add / LeakyReLU kernels.
 #include "common.h"
+#include "resize.h"
 
 namespace {
 
@@ -18,22 +19,6 @@ struct CsaArgs {
   float *out;
   int N, C, H, W, act;
 };
-
-// PyTorch upsample_bilinear2d, align_corners=False: src = scale*(dst+0.5)-0.5, clamped at 0;
-// i1 = (int)src; i1p = i1 < in-1; lambda = src - i1.
-__device__ __forceinline__ float bilinear_resize(const float *__restrict__ im, int ih, int iw,
-                                                 float sh, float sw, int y, int x) {
-  float hr = sh * ((float)y + 0.5f) - 0.5f;
-  hr = hr < 0.f ? 0.f : hr;
-  float wr = sw * ((float)x + 0.5f) - 0.5f;
-  wr = wr < 0.f ? 0.f : wr;
-  const int h1 = (int)hr, w1 = (int)wr;
-  const int h1p = h1 < ih - 1 ? 1 : 0, w1p = w1 < iw - 1 ? 1 : 0;
-  const float h1l = hr - (float)h1, h0l = 1.f - h1l;
-  const float w1l = wr - (float)w1, w0l = 1.f - w1l;
-  const float *r0 = im + (long)h1 * iw, *r1 = im + (long)(h1 + h1p) * iw;
-  return h0l * (w0l * r0[w1] + w1l * r0[w1 + w1p]) + h1l * (w0l * r1[w1] + w1l * r1[w1 + w1p]);
-}
 
 // One thread = 4 consecutive output columns: the same-size term is read and the result written
 // as float4; resized terms (1/2, 1/4 resolution, L2-resident) are gathered per element.
@@ -130,16 +115,6 @@ __global__ __launch_bounds__(256) void csa_sum_scalar_kernel(CsaArgs a) {
   }
 }
 
-// Weight of input index i in output index o along one axis (the align_corners=False rule of
-// bilinear_resize): lambda0 if i is o's lower tap, lambda1 if its upper one (both at the edge).
-__device__ __forceinline__ float bilinear_axis_weight(int o, int i, float s, int in) {
-  float r = s * ((float)o + 0.5f) - 0.5f;
-  r = r < 0.f ? 0.f : r;
-  const int i1 = (int)r, i1p = i1 < in - 1 ? 1 : 0;
-  const float l1 = r - (float)i1, l0 = 1.f - l1;
-  return (i1 == i ? l0 : 0.f) + (i1 + i1p == i ? l1 : 0.f);
-}
-
 // Backward of the resize as a gather: each input element sums, in a fixed order, the output
 // gradients of the outputs whose 2x2 stencil covers it (source coordinate in (i-1, i+1)).
 // torch's CUDA backward scatters with atomics (and under deterministic algorithms falls back to a
@@ -188,17 +163,7 @@ __global__ __launch_bounds__(256) void resize_bilinear_fwd_kernel(const float *_
     const long t = e / ow;
     const int oy = (int)(t % oh);
     const long plane = t / oh;
-    // explicit FMAs: the contraction torch's kernel gets (tools/resize_lab.hip: bit-identical
-    // for this form only; plain or differently fused expressions differ in 2-40% of the outputs)
-    float ry = __builtin_fmaf(sh, (float)oy + 0.5f, -0.5f), rx = __builtin_fmaf(sw, (float)ox + 0.5f, -0.5f);
-    ry = ry < 0.f ? 0.f : ry;
-    rx = rx < 0.f ? 0.f : rx;
-    const int y1 = (int)ry, x1 = (int)rx;
-    const int y1p = y1 < ih - 1 ? iw : 0, x1p = x1 < iw - 1 ? 1 : 0;
-    const float ly1 = ry - (float)y1, ly0 = 1.f - ly1, lx1 = rx - (float)x1, lx0 = 1.f - lx1;
-    const float *p = x + plane * ih * iw + (long)y1 * iw + x1;
-    y[e] = __builtin_fmaf(ly0, __builtin_fmaf(lx0, p[0], lx1 * p[x1p]),
-                          ly1 * __builtin_fmaf(lx0, p[y1p], lx1 * p[y1p + x1p]));
+    y[e] = bilinear_resize_fma(x + plane * ih * iw, ih, iw, sh, sw, oy, ox);
   }
 }
 

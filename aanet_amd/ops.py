@@ -1116,6 +1116,147 @@ def resize_bilinear(x, size):
     return ResizeBilinearFunction.apply(x, size)
 
 
+# ------------------------------------------------- disparity loss and validation metrics ---
+LOSS_MAX_LEVELS = 8         # AANET_LOSS_MAX_LEVELS (include/aanet_mi355x.h)
+METRICS_MAX_THRESHOLDS = 8  # AANET_METRICS_MAX_THRESHOLDS
+
+
+def _require_mask(mask, like, name):
+    """A torch.bool mask (one byte per pixel) of `like`'s shape, contiguous, on its device."""
+    if mask.dtype != torch.bool:
+        raise TypeError(f"{name} must be torch.bool; it is {mask.dtype}")
+    if mask.shape != like.shape or mask.device != like.device:
+        raise ValueError(f"{name} must have the ground truth's shape and device")
+    if not mask.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _loss_arrays(preds, weights, grads=None):
+    k = len(preds)
+    arrays = [(ctypes.c_void_p * k)(*[t.data_ptr() for t in preds])]
+    if grads is not None:
+        arrays.append((ctypes.c_void_p * k)(*[t.data_ptr() for t in grads]))
+    return arrays + [(ctypes.c_int * k)(*[t.shape[1] for t in preds]),
+                     (ctypes.c_int * k)(*[t.shape[2] for t in preds]),
+                     (ctypes.c_float * k)(*[float(w) for w in weights])]
+
+
+def _check_loss_inputs(preds, gt, mask, weights, pseudo_gt, pseudo_mask):
+    if not 1 <= len(preds) <= LOSS_MAX_LEVELS:
+        raise ValueError(f"disp_loss takes 1..{LOSS_MAX_LEVELS} predictions")
+    if len(weights) != len(preds):
+        raise ValueError("one weight per prediction")
+    if (pseudo_gt is None) != (pseudo_mask is None):
+        raise ValueError("pseudo_gt and pseudo_mask go together")
+    require_gpu(gt, pseudo_gt, *preds, names=("gt", "pseudo_gt") + ("pred",) * len(preds))
+    if gt.dim() != 3 or any(p.dim() != 3 or p.shape[0] != gt.shape[0] for p in preds):
+        raise ValueError("disp_loss: predictions [B, h, w] and gt [B, H, W]")
+    _require_mask(mask, gt, "mask")
+    if pseudo_gt is not None:
+        if pseudo_gt.shape != gt.shape:
+            raise ValueError("pseudo_gt must have the ground truth's shape")
+        _require_mask(pseudo_mask, gt, "pseudo_mask")
+
+
+def disp_loss_forward(preds, gt, mask, weights, pseudo_gt=None, pseudo_mask=None):
+    """aanet_disp_loss_f32 -> (total [], per_level [L], pseudo_per_level [L], counts [2] int64:
+    the valid and the pseudo-valid pixels), all on the device.  No autograd (disp_loss)."""
+    _check_loss_inputs(preds, gt, mask, weights, pseudo_gt, pseudo_mask)
+    B, H, W = gt.shape
+    L = len(preds)
+    total = torch.empty((), device=gt.device, dtype=torch.float32)
+    per_level = torch.empty((L,), device=gt.device, dtype=torch.float32)
+    pseudo_per_level = torch.empty((L,), device=gt.device, dtype=torch.float32)
+    counts = torch.empty((2,), device=gt.device, dtype=torch.int64)
+    nbytes = _lib.lib().aanet_disp_loss_workspace_size(L, B, H, W)
+    if nbytes == 0:
+        raise ValueError("aanet_disp_loss_workspace_size: invalid shape")
+    ws = torch.empty((nbytes,), device=gt.device, dtype=torch.uint8)
+    call("aanet_disp_loss_f32", L, *_loss_arrays(preds, weights), ptr(gt), ptr(mask),
+         ptr(pseudo_gt), ptr(pseudo_mask), B, H, W, ptr(per_level), ptr(pseudo_per_level),
+         ptr(total), ptr(counts), ctypes.c_void_p(counts.data_ptr() + 8), ptr(ws), nbytes,
+         stream_of(gt))
+    return total, per_level, pseudo_per_level, counts
+
+
+def disp_loss_backward(preds, gt, mask, weights, pseudo_gt, pseudo_mask, grad_total, counts):
+    """aanet_disp_loss_bwd_f32 -> the gradients of `total` with respect to every prediction.
+    grad_total (0-dim) and counts (disp_loss_forward's) stay on the device."""
+    _check_loss_inputs(preds, gt, mask, weights, pseudo_gt, pseudo_mask)
+    require_gpu(grad_total, names=("grad_total",))
+    if grad_total.numel() != 1 or counts.dtype != torch.int64 or counts.numel() != 2 \
+            or counts.device != gt.device or not counts.is_contiguous():
+        raise ValueError("disp_loss_backward: grad_total is one value, counts two int64")
+    B, H, W = gt.shape
+    grads = [torch.empty_like(p) for p in preds]
+    call("aanet_disp_loss_bwd_f32", len(preds), *_loss_arrays(preds, weights, grads), ptr(gt),
+         ptr(mask), ptr(pseudo_gt), ptr(pseudo_mask), B, H, W, ptr(grad_total), ptr(counts),
+         ctypes.c_void_p(counts.data_ptr() + 8), stream_of(gt))
+    return grads
+
+
+class DispLossFunction(Function):
+    """The multi-scale disparity loss of train.disparity_loss (model.py:109-134) as one HIP pass
+    over the ground truth (aanet_disp_loss_f32) and a gather backward (aanet_disp_loss_bwd_f32):
+    no full-resolution temporary, no atomics, no host synchronisation.  Returns (total,
+    per_level, pseudo_per_level); only `total` is differentiable, with respect to the
+    predictions."""
+
+    @staticmethod
+    def forward(ctx, gt, mask, pseudo_gt, pseudo_mask, weights, *preds):
+        preds = [p.contiguous() for p in preds]
+        weights = tuple(float(w) for w in weights)
+        total, per_level, pseudo_per_level, counts = disp_loss_forward(
+            preds, gt, mask, weights, pseudo_gt, pseudo_mask)
+        ctx.weights, ctx.pseudo = weights, pseudo_gt is not None
+        extra = (pseudo_gt, pseudo_mask) if ctx.pseudo else ()
+        ctx.save_for_backward(gt, mask, counts, *extra, *preds)
+        ctx.mark_non_differentiable(per_level, pseudo_per_level)
+        return total, per_level, pseudo_per_level
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_total, _grad_levels, _grad_pseudo):
+        gt, mask, counts, *rest = ctx.saved_tensors
+        pseudo_gt, pseudo_mask = (rest[0], rest[1]) if ctx.pseudo else (None, None)
+        preds = rest[2:] if ctx.pseudo else rest
+        grads = disp_loss_backward(list(preds), gt, mask, ctx.weights, pseudo_gt, pseudo_mask,
+                                   grad_total.contiguous(), counts)
+        return (None,) * 5 + tuple(grads)
+
+
+def disp_loss(preds, gt, mask, weights, pseudo_gt=None, pseudo_mask=None):
+    """(total, per_level, pseudo_per_level) of the pyramid `preds` (coarse to fine, [B, h, w])
+    against gt [B, H, W] over the bool mask, weighted by `weights` (DispLossFunction)."""
+    return DispLossFunction.apply(gt, mask, pseudo_gt, pseudo_mask, tuple(weights), *preds)
+
+
+def disp_metrics(pred, gt, mask, thresholds):
+    """aanet_disp_metrics_f32 -> (values [2 + len(thresholds)] = [epe, d1, share of e > t ...] over
+    the valid pixels, count [] int64), both on the device.  pred [B, h, w] smaller than gt is
+    upsampled and scaled on the fly (model.py:320-325)."""
+    thresholds = [float(t) for t in thresholds]
+    if len(thresholds) > METRICS_MAX_THRESHOLDS:
+        raise ValueError(f"disp_metrics takes at most {METRICS_MAX_THRESHOLDS} thresholds")
+    pred = pred.detach()
+    require_gpu(pred, gt, names=("pred", "gt"))
+    if gt.dim() != 3 or pred.dim() != 3 or pred.shape[0] != gt.shape[0]:
+        raise ValueError("disp_metrics: pred [B, h, w] and gt [B, H, W]")
+    _require_mask(mask, gt, "mask")
+    B, H, W = gt.shape
+    nt = len(thresholds)
+    values = torch.empty((2 + nt,), device=gt.device, dtype=torch.float32)
+    count = torch.empty((), device=gt.device, dtype=torch.int64)
+    nbytes = _lib.lib().aanet_disp_metrics_workspace_size(B, H, W)
+    if nbytes == 0:
+        raise ValueError("aanet_disp_metrics_workspace_size: invalid shape")
+    ws = torch.empty((nbytes,), device=gt.device, dtype=torch.uint8)
+    call("aanet_disp_metrics_f32", ptr(pred), pred.shape[1], pred.shape[2], ptr(gt), ptr(mask),
+         B, H, W, nt, (ctypes.c_float * max(nt, 1))(*thresholds), ptr(values), ptr(count), ptr(ws),
+         nbytes, stream_of(gt))
+    return values, count
+
+
 DCN_BWD_ALGOS = {"auto": 0, "global": 1, "window": 2}  # AANET_DCN_BWD_* (include/aanet_mi355x.h)
 
 

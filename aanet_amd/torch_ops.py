@@ -11,7 +11,7 @@ reference's CUDA-only DCN does (nets/deform_conv/deform_conv.py:135-136).
     gx, goff, gmask, gw, gb = torch.ops.aanet.mdcn_backward(x, offset, mask, weight, gy, True,
                                                             1, 2, 2, 1, 2)
 """
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -186,5 +186,72 @@ def _(cost, negate):
     return cost.new_empty((B, 4 * H, 4 * W))
 
 
+# ------------------------------------------- disparity loss and validation metrics -------
+@torch.library.custom_op(f"{_NS}::disp_loss", mutates_args=(), device_types="cuda")
+def disp_loss(preds: List[Tensor], gt: Tensor, mask: Tensor, weights: List[float],
+              pseudo_gt: Optional[Tensor], pseudo_mask: Optional[Tensor]
+              ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """model.py:109-134 in one pass (ops.disp_loss_forward) -> (total [], per_level [L],
+    pseudo_per_level [L], counts [2] int64: valid and pseudo-valid pixels)."""
+    return ops.disp_loss_forward([p.contiguous() for p in preds], gt, mask, weights, pseudo_gt,
+                                 pseudo_mask)
+
+
+@disp_loss.register_fake
+def _(preds, gt, mask, weights, pseudo_gt, pseudo_mask):
+    n = len(preds)
+    return (gt.new_empty(()), gt.new_empty((n,)), gt.new_empty((n,)),
+            gt.new_empty((2,), dtype=torch.int64))
+
+
+@torch.library.custom_op(f"{_NS}::disp_loss_backward", mutates_args=(), device_types="cuda")
+def disp_loss_backward(preds: List[Tensor], gt: Tensor, mask: Tensor, weights: List[float],
+                       pseudo_gt: Optional[Tensor], pseudo_mask: Optional[Tensor],
+                       grad_total: Tensor, counts: Tensor) -> List[Tensor]:
+    """Gradients of disp_loss's `total` with respect to every prediction (the gather of
+    ops.disp_loss_backward); grad_total and counts are device values."""
+    return ops.disp_loss_backward([p.contiguous() for p in preds], gt, mask, weights, pseudo_gt,
+                                  pseudo_mask, grad_total.contiguous(), counts)
+
+
+@disp_loss_backward.register_fake
+def _(preds, gt, mask, weights, pseudo_gt, pseudo_mask, grad_total, counts):
+    return [torch.empty_like(p, memory_format=torch.contiguous_format) for p in preds]
+
+
+def _disp_loss_setup(ctx, inputs, output):
+    preds, gt, mask, weights, pseudo_gt, pseudo_mask = inputs
+    ctx.n, ctx.weights, ctx.pseudo = len(preds), list(weights), pseudo_gt is not None
+    extra = (pseudo_gt, pseudo_mask) if ctx.pseudo else ()
+    ctx.save_for_backward(gt, mask, output[3], *extra, *preds)
+    ctx.mark_non_differentiable(output[1], output[2], output[3])
+
+
+def _disp_loss_backward_formula(ctx, grad_total, _grad_levels, _grad_pseudo, _grad_counts):
+    gt, mask, counts, *rest = ctx.saved_tensors
+    pseudo_gt, pseudo_mask = (rest[0], rest[1]) if ctx.pseudo else (None, None)
+    preds = list(rest[2:] if ctx.pseudo else rest)
+    grads = disp_loss_backward(preds, gt, mask, ctx.weights, pseudo_gt, pseudo_mask, grad_total,
+                               counts)
+    return list(grads), None, None, None, None, None
+
+
+torch.library.register_autograd(f"{_NS}::disp_loss", _disp_loss_backward_formula,
+                                setup_context=_disp_loss_setup)
+
+
+@torch.library.custom_op(f"{_NS}::disp_metrics", mutates_args=(), device_types="cuda")
+def disp_metrics(pred: Tensor, gt: Tensor, mask: Tensor,
+                 thresholds: List[float]) -> Tuple[Tensor, Tensor]:
+    """metric.py in one pass (ops.disp_metrics) -> ([epe, d1, share of e > t ...], valid count)."""
+    return ops.disp_metrics(pred.contiguous(), gt, mask, thresholds)
+
+
+@disp_metrics.register_fake
+def _(pred, gt, mask, thresholds):
+    return gt.new_empty((2 + len(thresholds),)), gt.new_empty((), dtype=torch.int64)
+
+
 OPS = ("mdcn_forward", "mdcn_backward", "corr_volume", "corr_volume_backward", "disp_regress",
-       "disp_regress_backward", "disp_regress_up4")
+       "disp_regress_backward", "disp_regress_up4", "disp_loss", "disp_loss_backward",
+       "disp_metrics")

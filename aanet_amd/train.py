@@ -19,8 +19,8 @@ so the all-reduce is a single large ring over xGMI instead of the default 25 MB 
 gradients are bucket views (no extra copy).  The DCN backward is the HIP one; with
 torch.use_deterministic_algorithms(True) it is the bit-reproducible form
 (aanet_mdcn_bwd_det_f32) -- the HIP cost-volume and regression backwards are gathers and are
-reproducible either way; the loss's bilinear upsampling backward is torch's and follows torch's
-own deterministic-algorithms rules.
+reproducible either way, and so are the loss's (ops.resize_bilinear; with Trainer(fused_loss=True)
+the whole loss is two HIP launches forward and one gather per scale backward).
 """
 import contextlib
 
@@ -82,6 +82,26 @@ def disparity_loss(pred_pyramid, gt_disp, mask, weights=None, pseudo_gt=None, ps
             ploss = (F.smooth_l1_loss(pred, pseudo_gt, reduction="none") * pmaskf).sum() / pcount
             total = total + w * ploss
     return total, per_scale
+
+
+def disparity_loss_fused(pred_pyramid, gt_disp, mask, weights=None, pseudo_gt=None,
+                          pseudo_mask=None):
+    """disparity_loss on the fused HIP kernels (ops.disp_loss): one pass over gt / mask for all
+    scales, and a gather backward without full-resolution temporaries, atomics or host
+    synchronisation.  Same signature and return shape; fp32 tensors on the GPU take the HIP op,
+    anything else disparity_loss."""
+    tensors = list(pred_pyramid) + [gt_disp] + ([] if pseudo_gt is None else [pseudo_gt])
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return disparity_loss(pred_pyramid, gt_disp, mask, weights, pseudo_gt, pseudo_mask)
+    if weights is None:
+        weights = pyramid_weights(len(pred_pyramid))
+    if len(weights) != len(pred_pyramid):
+        raise ValueError("one weight per prediction")
+    if pseudo_gt is not None:
+        pseudo_gt, pseudo_mask = pseudo_gt.contiguous(), pseudo_mask.contiguous()
+    total, per_level, _ = ops.disp_loss(list(pred_pyramid), gt_disp.contiguous(),
+                                        mask.contiguous(), weights, pseudo_gt, pseudo_mask)
+    return total, list(per_level.unbind(0))
 
 
 def param_groups(model, lr):
@@ -180,13 +200,16 @@ class Trainer:
     """One optimizer step per `accumulation_steps` micro-batches (model.py:64-153)."""
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, accumulation_steps=1,
-                 highest_loss_only=False, max_disp=192, engine_convs=None, capturable=False):
+                 highest_loss_only=False, max_disp=192, engine_convs=None, capturable=False,
+                 fused_loss=False):
         """max_disp: the image-resolution disparity range of the valid mask (train.py --max_disp,
         default 192), NOT the cost-volume D.  engine_convs: run the plain convs on the HIP engine
         (use_engine_convs); default: when the model is on the GPU (measured round 5: the training
         step 17.3 -> 15.7 ms against MIOpen, whose NHWC kernels transpose around every NCHW conv;
         under torch.use_deterministic_algorithms(True) MIOpen has only its naive kernels).  capturable: Adam keeps its step count on
-        the device, so that the step can be captured into a HIP graph (graph_step)."""
+        the device, so that the step can be captured into a HIP graph (graph_step).  fused_loss:
+        step and graph_step compute the loss with disparity_loss_fused instead of
+        disparity_loss."""
         if engine_convs is None:
             params = list(model.parameters())
             engine_convs = bool(params) and all(p.is_cuda for p in params)
@@ -196,6 +219,7 @@ class Trainer:
         self.accumulation_steps = accumulation_steps
         self.highest_loss_only = highest_loss_only
         self.max_disp = max_disp
+        self.fused_loss = fused_loss
         # fused Adam (one multi-tensor kernel per step) when every parameter is on the GPU: the
         # foreach form's capturable branch divides by 0-dim step tensors, which this torch build
         # runs as two broadcast kernels PER PARAMETER (~360 launches, ~2 ms of a 20 ms step);
@@ -227,8 +251,8 @@ class Trainer:
                     pyramid = self.model(left_feature, right_feature)
                     if self.highest_loss_only:
                         pyramid = [pyramid[-1]]
-                    total, _ = disparity_loss(pyramid, gt_disp, mask,
-                                              pyramid_weights(len(pyramid), self.highest_loss_only))
+                    total, _ = self.loss_fn(pyramid, gt_disp, mask,
+                                            pyramid_weights(len(pyramid), self.highest_loss_only))
                     total.backward()
                 self.optimizer.step()
                 return total.detach()
@@ -272,6 +296,10 @@ class Trainer:
         self._graph.replay()
         return self._graph_loss
 
+    @property
+    def loss_fn(self):
+        return disparity_loss_fused if self.fused_loss else disparity_loss
+
     def valid_mask(self, disp):
         """model.py:71,75: 0 < d < max_disp."""
         return (disp > 0) & (disp < self.max_disp)
@@ -299,9 +327,9 @@ class Trainer:
             pyramid = self.model(left_feature, right_feature)
             if self.highest_loss_only:
                 pyramid = [pyramid[-1]]
-            total, _ = disparity_loss(pyramid, gt_disp, mask,
-                                      pyramid_weights(len(pyramid), self.highest_loss_only),
-                                      pseudo_gt, pseudo_mask)
+            total, _ = self.loss_fn(pyramid, gt_disp, mask,
+                                    pyramid_weights(len(pyramid), self.highest_loss_only),
+                                    pseudo_gt, pseudo_mask)
             (total / self.accumulation_steps).backward()
         if boundary:
             self.optimizer.step()

@@ -537,6 +537,66 @@ int aanet_resize_bilinear_f32(const float *x, float *y, long planes, int in_h, i
 int aanet_resize_bilinear_bwd_f32(const float *grad_out, float *grad_in, long planes, int in_h,
                                   int in_w, int out_h, int out_w, aanet_stream_t stream);
 
+/* The multi-scale disparity loss of the training step (model.py:109-134) in one pass over the
+ * ground truth.  preds (a HOST array of `levels` device pointers, 1 <= levels <=
+ * AANET_LOSS_MAX_LEVELS) are the pyramid's disparities [b, pred_h[k], pred_w[k]]; pred_h, pred_w
+ * and weights are host arrays too and are read during the call.  gt [b, h, w]; mask [b, h, w],
+ * one byte per pixel (non-zero = valid; torch bool); pseudo_gt / pseudo_mask: the optional pseudo
+ * ground truth (model.py:126-134), both NULL or both given.
+ * A level with pred_w[k] == w (which needs pred_h[k] == h: AANET_EINVAL otherwise) is read as it
+ * is; every other level is upsampled on the fly exactly as aanet_resize_bilinear_f32 does (bit for
+ * bit) and multiplied by (float)w / (float)pred_w[k] in a separate fp32 multiply.  Per level:
+ * smooth-L1 with beta 1 of (level - gt), summed over the pixels whose mask is set -- selected, not
+ * multiplied: masked-out gt may be inf or NaN -- and divided by their count (NaN when there is
+ * none).  A level larger than gt is AANET_EUNSUPPORTED.
+ * Outputs (device): per_level[levels] and pseudo_per_level[levels] (zeros without pseudo_gt), the
+ * masked means; total = sum_k weights[k] * (per_level[k] + pseudo_per_level[k]); count and
+ * pseudo_count, the numbers of valid pixels.
+ * Deterministic: fp32 sums per thread, a fixed-shape tree per workgroup, one partial per workgroup
+ * in `workspace` (device, aanet_disp_loss_workspace_size(...) bytes), added in workgroup order in
+ * double by a second launch; integer counts; no atomics.  No host synchronisation. */
+enum { AANET_LOSS_MAX_LEVELS = 8 };
+size_t aanet_disp_loss_workspace_size(int levels, int b, int h, int w);
+int aanet_disp_loss_f32(int levels, const float *const *preds, const int *pred_h,
+                        const int *pred_w, const float *weights, const float *gt,
+                        const unsigned char *mask, const float *pseudo_gt,
+                        const unsigned char *pseudo_mask, int b, int h, int w, float *per_level,
+                        float *pseudo_per_level, float *total, long *count, long *pseudo_count,
+                        void *workspace, size_t workspace_bytes, aanet_stream_t stream);
+
+/* Backward of aanet_disp_loss_f32 with respect to every level: grad_preds (a host array of device
+ * pointers, [b, pred_h[k], pred_w[k]] each) are OVERWRITTEN, every element.  A gather per
+ * prediction element over the outputs whose 2x2 stencil covers it (the form of
+ * aanet_resize_bilinear_bwd_f32), in a fixed order that depends on the shapes only:
+ *   axis weights x scale_k x clamp(d, -1, 1) [mask] x grad_total x weights[k] / count
+ * plus the pseudo term with pseudo_count; d is recomputed from preds[k] and gt, nothing of the
+ * ground truth's size is stored.  grad_total (the gradient of `total`), count and pseudo_count
+ * (the forward's outputs; pseudo_count may be NULL without pseudo_gt) are DEVICE values read by
+ * the kernels: no host synchronisation, so forward and backward capture into a HIP graph.
+ * Bit-reproducible (no atomics). */
+int aanet_disp_loss_bwd_f32(int levels, const float *const *preds, float *const *grad_preds,
+                            const int *pred_h, const int *pred_w, const float *weights,
+                            const float *gt, const unsigned char *mask, const float *pseudo_gt,
+                            const unsigned char *pseudo_mask, int b, int h, int w,
+                            const float *grad_total, const long *count, const long *pseudo_count,
+                            aanet_stream_t stream);
+
+/* The validation metrics of metric.py (model.py:142-148, 320-341) in one pass: pred
+ * [b, pred_h, pred_w] (upsampled and scaled as in aanet_disp_loss_f32 when it is smaller than gt,
+ * model.py:320-325), gt and mask [b, h, w] as above; thresholds: a HOST array of num_thresholds
+ * (0 .. AANET_METRICS_MAX_THRESHOLDS) values.  With e = |gt - pred| over the valid pixels:
+ *   out[0] = mean e (EPE); out[1] = share of e > 3 and e / gt > 0.05 (D1; a correctly rounded
+ *   fp32 division); out[2 + j] = share of e > thresholds[j]
+ * (device, 2 + num_thresholds floats; NaN without a valid pixel) and *count (device) = the number
+ * of valid pixels.  The counts are integers, hence exact; sum e follows the partial scheme of
+ * aanet_disp_loss_f32, with `workspace` (device) of aanet_disp_metrics_workspace_size(...) bytes. */
+enum { AANET_METRICS_MAX_THRESHOLDS = 8 };
+size_t aanet_disp_metrics_workspace_size(int b, int h, int w);
+int aanet_disp_metrics_f32(const float *pred, int pred_h, int pred_w, const float *gt,
+                           const unsigned char *mask, int b, int h, int w, int num_thresholds,
+                           const float *thresholds, float *out, long *count, void *workspace,
+                           size_t workspace_bytes, aanet_stream_t stream);
+
 /* deform_conv_cuda.cpp:571-685 (modulated_deform_conv_cuda_backward) + kernel.cu:635-767.
  * grad_x, grad_offset, grad_mask are OVERWRITTEN; grad_weight and grad_bias (may be NULL)
  * ACCUMULATE, as in the reference (cpp:660-671). */
