@@ -455,8 +455,9 @@ class AdaptiveAggregation(FoldCacheMixin, nn.Module):
     def _post_for(self, i, regress):
         """The post stage of fusion i's scale-0 tail kernel (eval, fused): the next module's
         bottleneck conv1 + BN1 + ReLU (NHWC), or for the last fusion, with `regress`, final_conv +
-        the soft-argmin.  None when the shapes do not fit (64 channels at scale 0, 1x1, one
-        stage block)."""
+        the soft-argmin.  None when the shapes do not fit (64 channels at scale 0, 1x1; the
+        conv1 stage also needs one stage block in the next fusion, the last fusion's stage runs
+        in its last block's tail however many blocks a stage has)."""
         if i + 1 < self.num_fusions:
             if get_option(self, "post_fusion") != "all":
                 return None

@@ -7,8 +7,12 @@ environment: two models in one process can run different schedules, and every op
 exercise is passed to the module under test.
 
 Every option changes only the kernel schedule of the eval fast path; the result is the same
-computation (bit-identical, or for `concurrent_scales` / `s2_sums` / `dense_grouped` within fp32
-summation order; tests/test_gpu_production.py, test_gpu_post.py, test_gpu_dense_grouped.py).
+computation: bit-identical for `concurrent_scales`, `prep_stream` and `batch_chains` (the same
+kernels on the same inputs, on other streams); within fp32 summation order for `s2_sums`,
+`dense_grouped`, `pipeline`, and for `post_fusion` where a tail kernel takes a post stage (where
+none does -- sizes that refuse the CSA epilogue, a scale-0 width other than 64 -- the setting
+changes nothing).  tests/test_gpu_production.py, test_gpu_post.py, test_gpu_dense_grouped.py,
+test_gpu_hotpath_sweep.py.
 
   concurrent_scales  True: the coarse scales run on side HIP streams beside the scale-0 chain;
                      False: one stream.                              (AdaptiveAggregation)

@@ -39,10 +39,11 @@ class OracleMDCN(torch.autograd.Function):
     def forward(ctx, x, offset, mask, weight, bias, dilation, dg):
         ctx.save_for_backward(x, offset, mask, weight)
         ctx.dilation, ctx.dg, ctx.with_bias = dilation, dg, bias is not None
+        dtype = np.float64 if x.dtype == torch.float64 else np.float32
         out = oracle.mdcn_forward(x.detach().numpy(), offset.detach().numpy(),
                                   mask.detach().numpy(), weight.detach().numpy(),
                                   None if bias is None else bias.detach().numpy(), 1, dilation,
-                                  dilation, 1, dg)
+                                  dilation, 1, dg, dtype=dtype)
         return torch.from_numpy(out)
 
     @staticmethod
@@ -86,9 +87,13 @@ def bottleneck(x, sd, p, deform, dilation=2, dg=2):
     return F.relu(out + x)
 
 
-def aa_module(x, sd, p, num_scales, num_out, deform, dilation=2, dg=2):
-    """nets/aggregation.py:375-402."""
-    x = [bottleneck(x[i], sd, f"{p}.branches.{i}.0", deform, dilation, dg) for i in range(num_scales)]
+def aa_module(x, sd, p, num_scales, num_out, deform, dilation=2, dg=2, num_blocks=1):
+    """nets/aggregation.py:375-402 (num_blocks: the module's bottlenecks per branch,
+    branches.{i}.{b}, run in order)."""
+    x = list(x)
+    for i in range(num_scales):
+        for b in range(num_blocks):
+            x[i] = bottleneck(x[i], sd, f"{p}.branches.{i}.{b}", deform, dilation, dg)
     if num_scales == 1:
         return x
     fused = []
@@ -118,19 +123,33 @@ def aa_module(x, sd, p, num_scales, num_out, deform, dilation=2, dg=2):
 
 
 def adaptive_aggregation(volumes, sd, num_scales=3, num_fusions=6, num_deform_blocks=3,
-                         intermediate_supervision=True, dilation=2, dg=2):
-    """nets/aggregation.py:406-464 (eval mode), sd keys without the 'aggregation.' prefix."""
+                         intermediate_supervision=True, dilation=2, dg=2, num_stage_blocks=1,
+                         dtype=np.float32):
+    """nets/aggregation.py:406-464 (eval mode), sd keys without the 'aggregation.' prefix.
+    dtype np.float64: the state dict and the volumes are cast up and every step (the C oracle's
+    DCN included) runs in double; the float32 default computes what it always has."""
+    if np.dtype(dtype) == np.float64:
+        sd = {k: np.asarray(v, np.float64) if np.asarray(v).dtype.kind == "f" else v
+              for k, v in sd.items()}
+        volumes = [np.asarray(v, np.float64) for v in volumes]
     x = [_t(v) for v in volumes]
     for f in range(num_fusions):
         num_out = num_scales if intermediate_supervision else (1 if f == num_fusions - 1 else num_scales)
         deform = f >= num_fusions - num_deform_blocks
-        x = aa_module(x, sd, f"fusions.{f}", num_scales, num_out, deform, dilation, dg)
+        x = aa_module(x, sd, f"fusions.{f}", num_scales, num_out, deform, dilation, dg,
+                      num_stage_blocks)
     n_final = num_scales if intermediate_supervision else 1
     return [_conv(x[i], sd, f"final_conv.{i}") for i in range(n_final)]
 
 
-def hot_path(left_pyr, right_pyr, sd, max_disp, **kw):
-    """cost volume pyramid -> AdaptiveAggregation -> regression in reverse order (aanet.py:146-167)."""
-    vols = oracle.cost_volume_pyramid(left_pyr, right_pyr, max_disp)
+def hot_path(left_pyr, right_pyr, sd, max_disp, dtype=np.float32, with_aggregation=False, **kw):
+    """cost volume pyramid -> AdaptiveAggregation -> regression in reverse order (aanet.py:146-167).
+    num_scales < 3 takes the first num_scales volumes (aanet.py:150-151 for one scale).
+    with_aggregation: -> (disparities, aggregated cost volumes in scale order)."""
+    vols = oracle.cost_volume_pyramid(left_pyr, right_pyr, max_disp, dtype=dtype)
+    vols = vols[:kw.get("num_scales", 3)]
+    if np.dtype(dtype) == np.float64:
+        kw["dtype"] = dtype
     aggs = [a.detach().numpy() for a in adaptive_aggregation(vols, sd, **kw)]
-    return [oracle.disp_regress(aggs[len(aggs) - 1 - i]) for i in range(len(aggs))]
+    disps = [oracle.disp_regress(aggs[len(aggs) - 1 - i], dtype=dtype) for i in range(len(aggs))]
+    return (disps, aggs) if with_aggregation else disps

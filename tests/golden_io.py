@@ -95,6 +95,18 @@ def synthetic_pyramid(B, C, H, W, seed, num_scales=3, channels=None):
     return left, right
 
 
+def synthetic_pyramid_sizes(B, C, sizes, seed):
+    """synthetic_pyramid with explicit per-scale (H, W) `sizes` (a pyramid whose coarse scales
+    are ceil- or floor-halved, or one row high): seeded N(0,1) (left, right) lists of
+    [B, C, H_s, W_s] tensors.  Its own generator stream (seed base 7000): no fixture depends on
+    it, and synthetic_pyramid's draws are untouched."""
+    import torch
+    g = torch.Generator().manual_seed(7000 + seed)
+    left = [torch.randn(B, C, h, w, generator=g) for h, w in sizes]
+    right = [torch.randn(B, C, h, w, generator=g) for h, w in sizes]
+    return left, right
+
+
 def production_case(tag):
     """(fixture, numpy state dict of `aggregation.*` without the prefix, left pyramid, right
     pyramid) of a make_production_golden.py fixture: the weights are rebuilt by name on our own
