@@ -33,6 +33,7 @@ _SIGNATURES = {
     "aanet_disp_regress_f32": [_P, _P, _I, _I, _I, _I, _I, _P],
     "aanet_disp_regress_bwd_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "aanet_disp_regress_up4_f32": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "aanet_disp_regress_up4_bwd_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "aanet_disp_warp_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "aanet_disp_warp_bwd_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "aanet_mdcn_fwd_f32": [_P, _P, _P, _P, _P, _P] + [_I] * 12 + [_P],

@@ -1,7 +1,7 @@
 """Drop-in replacements for the reference's modules: the hot path (nets/cost.py,
 nets/estimation.py, nets/aggregation.py, nets/deform.py, nets/deform_conv/) and, around it, the
 feature extractors, refinement, warp, 3-D aggregators and the full AANet model."""
-from .aanet import AANet  # noqa: F401
+from .aanet import AANet, set_train_up4  # noqa: F401
 from .aggregation import AdaptiveAggregation, AdaptiveAggregationModule  # noqa: F401
 from .aggregation3d import (GCNetAggregation, PSMNetBasicAggregation,  # noqa: F401
                             PSMNetHGAggregation, PSMNetHourglass, StereoNetAggregation)

@@ -29,10 +29,23 @@ _REFINEMENT = {'stereonet': StereoNetRefinement, 'stereodrnet': StereoDRNetRefin
                'hourglass': HourglassRefinement}
 
 
+def set_train_up4(model, on=True):
+    """Opt a model (an AANet, or a bare PSMNet aggregator) in to or out of the fused training
+    tail: sets `aanet_train_up4` on it and on its aggregator; returns the model."""
+    for m in (model, getattr(model, "aggregation", None)):
+        if hasattr(m, "aanet_train_up4"):
+            m.aanet_train_up4 = bool(on)
+    return model
+
+
 _AGG3D = (GCNetAggregation, PSMNetBasicAggregation, PSMNetHGAggregation, StereoNetAggregation)
 
 
 class AANet(FoldCacheMixin, nn.Module):
+    # opt-in (set_train_up4): in training / under autograd on the HIP device the PSMNet
+    # aggregators' tail runs ops.DisparityRegressionUp4Function on their low-resolution costs
+    aanet_train_up4 = False
+
     def __init__(self, max_disp, useFeatureAtt=1, num_downsample=2, feature_type='aanet',
                  no_feature_mdconv=False, feature_pyramid=False, feature_pyramid_network=False,
                  feature_similarity='correlation', aggregation_type='adaptive', num_scales=3,
@@ -157,7 +170,10 @@ class AANet(FoldCacheMixin, nn.Module):
         fine.  In eval without autograd the tails are fused: the adaptive aggregator's final_conv
         + soft-argmin in its last kernel, the PSMNet aggregators' x4 upsampling inside the
         soft-argmin (ops.disp_regress_up4 on their low-resolution cost).  Training, autograd and
-        `aanet_fuse = False` run the reference op order."""
+        `aanet_fuse = False` run the reference op order; with `aanet_train_up4` on (set_train_up4)
+        the PSMNet aggregators' tail is then ops.DisparityRegressionUp4Function on each
+        low-resolution cost, in the order of disparity_computation, and no [B, 4D, 4H, 4W] volume
+        is made."""
         if isinstance(self.aggregation, AdaptiveAggregation):
             # eval, one output scale: final_conv + the soft-argmin may run in the last tail
             # kernel's epilogue (AdaptiveAggregation._run)
@@ -173,6 +189,12 @@ class AANet(FoldCacheMixin, nn.Module):
             cost = self.aggregation(cost_volume, upsample=False)[0]
             return [ops.disp_regress_up4(cost.squeeze(1).contiguous(),
                                          negate=not self.disparity_estimation.match_similarity)]
+        elif isinstance(self.aggregation, (PSMNetBasicAggregation, PSMNetHGAggregation)) and \
+                self.aanet_train_up4 and self.aggregation.aanet_train_up4 and \
+                cost_volume.is_cuda and not use_fused(self.aggregation, cost_volume):
+            negate = not self.disparity_estimation.match_similarity
+            return [ops.DisparityRegressionUp4Function.apply(cost.squeeze(1), negate)
+                    for cost in reversed(self.aggregation(cost_volume, upsample=False))]
         else:
             aggregation = self.aggregation(cost_volume)
         return self.disparity_computation(aggregation)

@@ -27,6 +27,9 @@ The two ends: in a fused AANet the volume arrives channels_last_3d from csrc/cos
 (no layout copy in front of the first conv), and the PSMNet aggregators called with
 `upsample=False` return their low-resolution cost for ops.disp_regress_up4, which upsamples x4
 inside the soft-argmin (nets/aanet.py aggregation_and_disparity; switches in nets/_fuse.py).
+With the opt-in `aanet_train_up4` (nets.set_train_up4) they also do so on the reference op order
+on the HIP device -- training mode, autograd -- where ops.DisparityRegressionUp4Function takes the
+low-resolution costs (three from the hourglass in training mode) forward and backward.
 """
 import torch
 import torch.nn as nn
@@ -83,7 +86,14 @@ def _up4(cost):
 def _low_res_only():
     return ValueError("upsample=False is the fused eval path's (eval mode, no autograd, HIP "
                       "device, aanet_fuse on): this call runs the reference op order, which "
-                      "always upsamples")
+                      "always upsamples (aanet_train_up4 on a HIP device lifts this)")
+
+
+def _train_up4(module, cost):
+    """Whether a PSMNet aggregator on the reference op order (training, autograd) may hand back
+    its low-resolution costs: the opt-in `aanet_train_up4` (nets.set_train_up4) on the HIP device,
+    where ops.DisparityRegressionUp4Function upsamples them inside the soft-argmin."""
+    return module.aanet_train_up4 and cost.is_cuda
 
 
 class StereoNetAggregation(FoldCacheMixin, nn.Module):
@@ -107,6 +117,8 @@ class StereoNetAggregation(FoldCacheMixin, nn.Module):
 class PSMNetBasicAggregation(FoldCacheMixin, nn.Module):
     """aggregation.py:93-138: 12 3-D convs (one shared conv1 block), x4 trilinear upsampling."""
 
+    aanet_train_up4 = False  # nets.set_train_up4: upsample=False also under training / autograd
+
     def __init__(self, max_disp):
         super(PSMNetBasicAggregation, self).__init__()
         self.max_disp = max_disp
@@ -121,20 +133,22 @@ class PSMNetBasicAggregation(FoldCacheMixin, nn.Module):
 
     @fp32_convs
     def forward(self, cost, upsample=True):
-        """upsample=False (fused eval path only, else ValueError): the low-resolution
-        [B, 1, D, H, W] cost in a one-element list, for ops.disp_regress_up4."""
+        """upsample=False (the fused eval path, or aanet_train_up4 on the HIP device; else
+        ValueError): the low-resolution [B, 1, D, H, W] cost in a one-element list, for
+        ops.disp_regress_up4 / ops.DisparityRegressionUp4Function."""
         if use_fused(self, cost):
             cost0 = _chain(self.dres0, cost)
             for name in ("dres1", "dres2", "dres3", "dres4"):
                 cost0 = _chain(getattr(self, name), cost0, residual=cost0)
             low = _chain(self.classify, cost0)
             return [_up4(low)] if upsample else [low]
-        if not upsample:
+        if not upsample and not _train_up4(self, cost):
             raise _low_res_only()
         cost0 = self.dres0(cost)
         for name in ("dres1", "dres2", "dres3", "dres4"):
             cost0 = getattr(self, name)(cost0) + cost0
-        return [_up4(self.classify(cost0))]
+        low = self.classify(cost0)
+        return [_up4(low)] if upsample else [low]
 
 
 class PSMNetHourglass(FoldCacheMixin, nn.Module):
@@ -190,6 +204,8 @@ class PSMNetHourglass(FoldCacheMixin, nn.Module):
 class PSMNetHGAggregation(FoldCacheMixin, nn.Module):
     """aggregation.py:192-254: stacked hourglass; three cost outputs in training, one in eval."""
 
+    aanet_train_up4 = False  # nets.set_train_up4: upsample=False also under training / autograd
+
     def __init__(self, max_disp):
         super(PSMNetHGAggregation, self).__init__()
         self.max_disp = max_disp
@@ -207,11 +223,12 @@ class PSMNetHGAggregation(FoldCacheMixin, nn.Module):
 
     @fp32_convs
     def forward(self, cost, upsample=True):
-        """upsample=False (fused eval path only, else ValueError): the low-resolution
-        [B, 1, D, H, W] cost in a one-element list, for ops.disp_regress_up4."""
+        """upsample=False (the fused eval path, or aanet_train_up4 on the HIP device; else
+        ValueError): the low-resolution [B, 1, D, H, W] costs in a list (three in training mode),
+        for ops.disp_regress_up4 / ops.DisparityRegressionUp4Function."""
         if use_fused(self, cost):
             return self._forward_fused(cost, upsample)
-        if not upsample:
+        if not upsample and not _train_up4(self, cost):
             raise _low_res_only()
         cost0 = self.dres0(cost)
         cost0 = self.dres1(cost0) + cost0
@@ -224,9 +241,8 @@ class PSMNetHGAggregation(FoldCacheMixin, nn.Module):
         cost1 = self.classif1(out1)
         cost2 = self.classif2(out2) + cost1
         cost3 = self.classif3(out3) + cost2
-        if self.training:
-            return [_up4(cost1), _up4(cost2), _up4(cost3)]
-        return [_up4(cost3)]
+        costs = [cost1, cost2, cost3] if self.training else [cost3]
+        return [_up4(c) for c in costs] if upsample else costs
 
     def _forward_fused(self, cost, upsample=True):
         """Eval fast path: the same graph with every conv on the HIP kernels; the `+ cost0` adds

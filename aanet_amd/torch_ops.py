@@ -175,8 +175,8 @@ torch.library.register_autograd(f"{_NS}::disp_regress", _regress_backward_formul
 
 @torch.library.custom_op(f"{_NS}::disp_regress_up4", mutates_args=(), device_types="cuda")
 def disp_regress_up4(cost: Tensor, negate: bool) -> Tensor:
-    """x4 trilinear upsampling + soft-argmin in one kernel (ops.disp_regress_up4) -> [B, 4H, 4W].
-    Forward only: no autograd formula is registered."""
+    """x4 trilinear upsampling + soft-argmin in one kernel (ops.disp_regress_up4) -> [B, 4H, 4W];
+    its autograd formula is disp_regress_up4_backward."""
     return ops.disp_regress_up4(cost.detach().contiguous(), negate)
 
 
@@ -184,6 +184,26 @@ def disp_regress_up4(cost: Tensor, negate: bool) -> Tensor:
 def _(cost, negate):
     B, _, H, W = cost.shape
     return cost.new_empty((B, 4 * H, 4 * W))
+
+
+@torch.library.custom_op(f"{_NS}::disp_regress_up4_backward", mutates_args=(), device_types="cuda")
+def disp_regress_up4_backward(cost: Tensor, grad_disp: Tensor, negate: bool) -> Tensor:
+    """Gradient of disp_regress_up4 with respect to the cost (ops.disp_regress_up4_backward)."""
+    return ops.disp_regress_up4_backward(cost.contiguous(), grad_disp.contiguous(), negate)
+
+
+@disp_regress_up4_backward.register_fake
+def _(cost, grad_disp, negate):
+    return torch.empty_like(cost, memory_format=torch.contiguous_format)
+
+
+def _regress_up4_backward_formula(ctx, grad_disp):
+    (cost,) = ctx.saved_tensors
+    return disp_regress_up4_backward(cost, grad_disp, ctx.negate), None
+
+
+torch.library.register_autograd(f"{_NS}::disp_regress_up4", _regress_up4_backward_formula,
+                                setup_context=_regress_setup)
 
 
 # ------------------------------------------- disparity loss and validation metrics -------
@@ -254,4 +274,4 @@ def _(pred, gt, mask, thresholds):
 
 OPS = ("mdcn_forward", "mdcn_backward", "corr_volume", "corr_volume_backward", "disp_regress",
        "disp_regress_backward", "disp_regress_up4", "disp_loss", "disp_loss_backward",
-       "disp_metrics")
+       "disp_metrics", "disp_regress_up4_backward")

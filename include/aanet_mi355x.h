@@ -129,6 +129,15 @@ int aanet_disp_regress_bwd_f32(const float *cost, const float *grad_disp, float 
 int aanet_disp_regress_up4_f32(const float *cost, float *disp, int n, int d, int h, int w,
                                int negate, aanet_stream_t stream);
 
+/* Autograd of the above, replacing the backward of nets/aggregation.py:136, 252 +
+ * nets/estimation.py:13-30 (upsample_trilinear3d_backward of the softmax gradient): grad_disp
+ * [n, 4h, 4w] -> grad_cost [n, d, h, w] OVERWRITTEN.  One kernel, a gather with one owner per
+ * element (no atomics: bit-reproducible and independent of the batch), no workspace; neither the
+ * upsampled volume nor its gradient is stored.  AANET_EUNSUPPORTED where the index arithmetic
+ * would overflow (d > 2^22, h or w > 2^28, more than 2^31 - 1 workgroups). */
+int aanet_disp_regress_up4_bwd_f32(const float *cost, const float *grad_disp, float *grad_cost,
+                                   int n, int d, int h, int w, int negate, aanet_stream_t stream);
+
 /* ------------------------------------------------------------ disparity warp ----------- */
 
 /* nets/warp.py:41-64 (disp_warp, padding 'border'): img [n, c, h, w], disp [n, 1, h, w] ->
