@@ -377,7 +377,10 @@ def offset_conv_pack(conv):
 
 def offset_conv_eval(x, conv):
     """Eval offset_conv: the grouped direct kernel when x is channels-last and the conv fits
-    (offset_conv_pack), else the conv engine (conv_bn_act)."""
+    (offset_conv_pack), else the conv engine (conv_bn_act).  A packing does not promise an
+    instance: the kernel has (groups, 32-channel chunks per group) = (2, 1), (1, 1) and (1, 2),
+    so two groups of 64 channels (AANetFeature layer3) are refused at the launch and run on the
+    engine.  A channels-last 1x1 map is also NCHW-contiguous (is_nhwc false): engine as well."""
     pk = offset_conv_pack(conv) if is_nhwc(x) else None
     if pk is None:
         return conv_bn_act(x, conv)

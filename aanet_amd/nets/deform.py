@@ -162,8 +162,11 @@ class _BottleneckBase(FoldCacheMixin, nn.Module):
             cpg = width // c2.deformable_groups  # 32k-channel groups, or pairs of 16-channel ones
             nhwc = pw and width % 32 == 0 and (cpg % 32 == 0 or cpg == 16)
             # no tail kernel (AANetFeature layer3, width 128): a stride-1 modulated DCN still
-            # reads conv1's output channels-last -- the grouped offset conv (conv_g3) and the NHWC
-            # window form of the DCN
+            # reads conv1's output channels-last -- the NHWC window form of the DCN.  Its offset
+            # conv (128 -> 54, two groups of 64 channels) has a conv_g3 packing but no conv_g3
+            # instance (two K chunks per group exist for one group only): the kernel answers
+            # "unsupported" and offset_conv_eval runs it on the engine's halo tile
+            # (tests/stage_sweep.py, column g3_launch)
             dc0 = c2.deform_conv
             nhwc = nhwc or (not pw and c2.modulation and dc0.stride in (1, (1, 1)) and
                             dc0.groups == 1 and width % 32 == 0 and cpg % 32 == 0)

@@ -3,9 +3,15 @@ DCN and the HIP conv engine.
 
 Module trees (attribute names, Sequential indices) are the reference's, so its state dicts load
 unchanged.  In eval mode without autograd every plain 2-D conv with its BatchNorm and
-ReLU/LeakyReLU(0.2) is one HIP implicit-GEMM kernel (BN folded; residual adds in the epilogue);
-transposed convs and 3-D convs stay on PyTorch (MIOpen).  Training runs the reference's op
-order with autograd.
+ReLU/LeakyReLU(0.2) is one HIP kernel (BN folded; residual adds in the epilogue): the
+implicit-GEMM engine, or the dedicated 3x3 stride-2 kernel where s2_conv_ok holds (BasicConv
+asks it first: conv1a and conv1b's conv1, 32 -> 48, and the plain conv3a / conv3b conv1,
+64 -> 96; 48 inputs or 128 outputs go to the engine).  The hourglasses' 4x4 stride-2
+transposed convs run as the engine's phase conv + one assembly pass (ops.deconv2x), with
+Conv2x's concat in that pass; no 2-D conv of this file is left to aten in eval
+(tests/stage_sweep.py pins the launches per stage and size).  BasicConv's 3-D forms stay on
+PyTorch here (the 3-D aggregators have their own kernels, nets/aggregation3d.py).  Training
+runs the reference's op order with autograd.
 """
 import torch
 import torch.nn as nn

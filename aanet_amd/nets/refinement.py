@@ -3,8 +3,14 @@ and Hourglass (AANet+, with full-resolution HIP DCNs) refinement modules.
 
 The warp is the HIP disp_warp kernel; in eval mode without autograd every plain conv (+BN
 +LeakyReLU) runs on the HIP engine, and the last conv adds the upsampled disparity and applies
-the ReLU in its epilogue (`relu(disp + final_conv(x))` is one kernel).  Module trees are the
-reference's (checkpoint-compatible).
+the ReLU in its epilogue (`relu(disp + final_conv(x))` is one kernel).  The StereoDRNet /
+Hourglass stem (warp error + left image -> 16 ch, disparity -> 16 ch) is one kernel with a
+channels-last result (aanet_refine_stem_f32); the dilated stack runs channels-last; the
+hourglass is nets/feature.py's (stride-2 kernel, phase-conv deconvs, stride-2 DCNs on
+aanet_mdcn_fwd_fused_f32).  Its conv_start offset conv (32 -> 54, two 16-channel groups) has no
+grouped-kernel packing and runs on the engine as one block-diagonal conv (dense_grouped_ok).
+The disparity upsampling is F.interpolate, skipped when the disparity already has the image's
+size (StereoNet's always resizes).  Module trees are the reference's (checkpoint-compatible).
 """
 import torch
 import torch.nn as nn

@@ -398,10 +398,31 @@ def direct_fwd_ok(C, Co, kh, kw, stride, padding, dilation, groups, deformable_g
         padding == dilation >= 1
 
 
+def _two_columns(x, maps, kw, stride, padding, dilation):
+    """A one-column DCN input as the two-column one the kernels take (their samplers gather column
+    pairs: every aanet_mdcn_* entry answers "unsupported" for w < 2).  The added column is zeros,
+    which is what a sample reads outside the image, so output column 0 is unchanged; the offset /
+    mask maps are zero-padded to the wider output, whose extra columns the caller drops.
+    -> (x, maps, the output width of the one-column input)."""
+    wo, wo2 = _out_size(1, kw, stride, padding, dilation), _out_size(2, kw, stride, padding, dilation)
+    x2 = torch.nn.functional.pad(x, (0, 1))
+    x2 = x2.contiguous(memory_format=torch.channels_last) if _lib.is_nhwc(x) else x2.contiguous()
+    return x2, [torch.nn.functional.pad(m, (0, wo2 - wo)).contiguous() for m in maps], wo
+
+
+def _first_columns(res, wo, out):
+    res = res[..., :wo].contiguous()
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
 def mdcn_forward(x, offset, mask, weight, bias=None, stride=1, padding=0, dilation=1, groups=1,
                  deformable_groups=1, out=None, algo="auto"):
     """deform_conv_cuda.cpp:490-569 -> [N, Co, Ho, Wo].
 
+    A one-column input (W = 1) is run as a two-column one (_two_columns).
     algo "auto": the aggregation's DCN shapes (window_fwd_ok) run the LDS-window kernel on the
     split-bf16 contraction (weights packed by pack_weight_split, cached per weight version),
     the rest aanet_mdcn_fwd_f32 (16 channels in two groups: the direct kernel, dcn_small.hip;
@@ -409,6 +430,10 @@ def mdcn_forward(x, offset, mask, weight, bias=None, stride=1, padding=0, dilati
     require_gpu(x, offset, mask, weight, bias, names=("input", "offset", "mask", "weight", "bias"))
     N, C, H, W = x.shape
     Co, _, kh, kw = weight.shape
+    if W == 1:  # (the backward entries still refuse one column)
+        x2, (o2, m2), wo = _two_columns(x, (offset, mask), kw, stride, padding, dilation)
+        return _first_columns(mdcn_forward(x2, o2, m2, weight, bias, stride, padding, dilation,
+                                           groups, deformable_groups, None, algo), wo, out)
     Ho, Wo = _out_size(H, kh, stride, padding, dilation), _out_size(W, kw, stride, padding, dilation)
     if out is None:
         out = torch.empty((N, Co, Ho, Wo), device=x.device, dtype=x.dtype)
@@ -453,6 +478,11 @@ def mdcn_forward_fused(x, offset_mask, weight, bias=None, post_scale=None, post_
     Ho, Wo = _out_size(H, kh, stride, padding, dilation), _out_size(W, kw, stride, padding, dilation)
     if offset_mask.shape != (N, deformable_groups * 3 * K, Ho, Wo):
         raise ValueError(f"offset_mask shape {tuple(offset_mask.shape)} unexpected")
+    if W == 1:
+        x2, (om2,), wo = _two_columns(x, (offset_mask,), kw, stride, padding, dilation)
+        return _first_columns(
+            mdcn_forward_fused(x2, om2, weight, bias, post_scale, post_shift, act, stride, padding,
+                               dilation, deformable_groups, mask_scale, packed_weight, groups), wo, out)
     out = _own_out(out, (N, Co, Ho, Wo), x)
     bs = offset_mask.stride(0)
     mask_ptr = offset_mask.data_ptr() + 4 * deformable_groups * 2 * K * Ho * Wo

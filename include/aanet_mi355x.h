@@ -159,7 +159,10 @@ int aanet_disp_warp_bwd_f32(const float *img, const float *disp, const float *gr
 /* deform_conv_cuda.cpp:490-569 (modulated_deform_conv_cuda_forward) + kernel.cu:570-633.
  * x [n,c,h,w]; offset [n, dg*2*kh*kw, ho, wo]; mask [n, dg*kh*kw, ho, wo];
  * weight [co, c/groups, kh, kw]; bias [co] or NULL; out [n, co, ho, wo] OVERWRITTEN.
- * ho = (h + 2*pad - (dil*(kh-1)+1)) / stride + 1 (deform_conv.py:174-183). */
+ * ho = (h + 2*pad - (dil*(kh-1)+1)) / stride + 1 (deform_conv.py:174-183).
+ * w >= 2 in every aanet_mdcn_* entry (the samplers gather column pairs): AANET_EUNSUPPORTED
+ * otherwise.  A caller with one column pads a zero column and drops the extra output columns,
+ * which is exact (aanet_amd/ops.py _two_columns). */
 int aanet_mdcn_fwd_f32(const float *x, const float *offset, const float *mask, const float *weight,
                        const float *bias, float *out, int n, int c, int h, int w, int co, int kh,
                        int kw, int stride, int pad, int dil, int groups, int dg,

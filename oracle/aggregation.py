@@ -33,17 +33,20 @@ def _bn(x, sd, p):
 
 
 class OracleMDCN(torch.autograd.Function):
-    """CPU autograd wrapper of the C oracle (forward cpp:490-569, backward cpp:571-685)."""
+    """CPU autograd wrapper of the C oracle (forward cpp:490-569, backward cpp:571-685):
+    apply(x, offset, mask, weight, bias, dilation, dg[, stride]), padding = dilation; stride 1
+    unless given (the stride-2 DCNs of the feature and refinement hourglasses)."""
 
     @staticmethod
-    def forward(ctx, x, offset, mask, weight, bias, dilation, dg):
+    def forward(ctx, x, offset, mask, weight, bias, dilation, dg, *stride):
         ctx.save_for_backward(x, offset, mask, weight)
         ctx.dilation, ctx.dg, ctx.with_bias = dilation, dg, bias is not None
+        ctx.stride, ctx.extra = (int(stride[0]) if stride else 1), len(stride)
         dtype = np.float64 if x.dtype == torch.float64 else np.float32
         out = oracle.mdcn_forward(x.detach().numpy(), offset.detach().numpy(),
                                   mask.detach().numpy(), weight.detach().numpy(),
-                                  None if bias is None else bias.detach().numpy(), 1, dilation,
-                                  dilation, 1, dg, dtype=dtype)
+                                  None if bias is None else bias.detach().numpy(), ctx.stride,
+                                  dilation, dilation, 1, dg, dtype=dtype)
         return torch.from_numpy(out)
 
     @staticmethod
@@ -51,10 +54,11 @@ class OracleMDCN(torch.autograd.Function):
         x, offset, mask, weight = ctx.saved_tensors
         gx, go, gm, gw, gb = oracle.mdcn_backward(x.numpy(), offset.numpy(), mask.numpy(),
                                                   weight.numpy(), g.contiguous().numpy(),
-                                                  ctx.with_bias, 1, ctx.dilation, ctx.dilation,
-                                                  1, ctx.dg)
+                                                  ctx.with_bias, ctx.stride, ctx.dilation,
+                                                  ctx.dilation, 1, ctx.dg)
         t = torch.from_numpy
-        return t(gx), t(go), t(gm), t(gw), (t(gb) if gb is not None else None), None, None
+        return (t(gx), t(go), t(gm), t(gw), (t(gb) if gb is not None else None), None,
+                None) + (None,) * ctx.extra
 
 
 def _conv(x, sd, p, stride=1, padding=0, dilation=1, groups=1):

@@ -113,6 +113,7 @@ def census():
 # older suites cover: each needs a case with a ragged last tile.
 #   mode tail prec full cfg halo layout co_t ptt
 REQUIRED = [
+    (0, 0, 0, 0, 0, 0, 0, 32, 64),    # 5x5 stride-2 stem from the image (tests/stage_sweep.py)
     (0, 0, 0, 0, 0, 0, 0, 16, 128),
     (0, 0, 0, 0, 0, 0, 0, 64, 128),
     (0, 0, 0, 1, 0, 0, 0, 32, 64),
@@ -148,6 +149,8 @@ REQUIRED = [
     (0, 0, 1, 1, 0, 1, 1, 64, 128),
     (0, 0, 1, 1, 0, 2, 1, 32, 128),
     (0, 0, 1, 1, 0, 2, 1, 64, 128),
+    (0, 0, 1, 1, 0, 1, 3, 32, 128),   # _DilatedStack's dilation-1 / 2 convs, NHWC in and out
+    (0, 0, 1, 1, 0, 2, 3, 32, 128),
     (0, 0, 1, 1, 0, 4, 3, 32, 128),
     (0, 0, 1, 1, 0, 4, 3, 64, 128),
     (0, 1, 0, 0, 0, 0, 0, 16, 128),

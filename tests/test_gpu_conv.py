@@ -22,6 +22,7 @@ CONV_CASES = [
     (1, 16, 5, 13, 16, 3, 2, 1, 1, 1),
     (1, 5, 7, 9, 3, 3, 1, 1, 1, 1),          # tiny, odd channels
     (1, 96, 9, 33, 80, 3, 1, 1, 1, 1),       # Co > 64 (two co tiles)
+    (2, 3, 21, 30, 32, 5, 2, 2, 1, 1),       # StereoNet / GCNet stem: 5x5 stride 2 from the image
 ]
 
 
@@ -384,6 +385,10 @@ PHASE_CASES = [
     (1, 32, 19, 37, 32, 3),      # ragged phases: H, W not multiples of the dilation
     (1, 64, 21, 70, 64, 4),      # 64 channels (two K chunks), 64-channel tile
     (1, 32, 5, 9, 32, 8),        # image smaller than one dilation step in both directions
+    # the same blocks' dilation 1 and 2 convs, NHWC in and out (plain halo tiles, HALO 1 / 2): the
+    # form _DilatedStack runs, at a ragged size (tests/stage_sweep.py snr_37x61)
+    (2, 32, 37, 61, 32, 1),
+    (2, 32, 37, 61, 32, 2),
 ]
 
 
