@@ -48,6 +48,15 @@ _SIGNATURES = {
     "aanet_disp_loss_f32": [_I] + [_P] * 8 + [_I] * 3 + [_P] * 6 + [ctypes.c_size_t, _P],
     "aanet_disp_loss_bwd_f32": [_I] + [_P] * 9 + [_I] * 3 + [_P] * 4,
     "aanet_disp_metrics_f32": [_P, _I, _I, _P, _P] + [_I] * 4 + [_P] * 4 + [ctypes.c_size_t, _P],
+    "aanet_bn_act_plan": [_I] * 5 + [_P] * 3,
+    "aanet_bn_act_train_f32": [_P] * 7 + [_F, _F, _I] + [_P] * 3 + [_I] * 5
+    + [_P, ctypes.c_size_t, _P],
+    "aanet_bn_act_train_bwd_f32": [_P] * 6 + [_I] + [_P] * 4 + [_I] * 5 + [_P, ctypes.c_size_t, _P],
+    "aanet_bn_act_stats_f32": [_P] + [_I] * 4 + [_P, _P, ctypes.c_size_t, _P],
+    "aanet_bn_act_finish_f32": [_P, _I, _I, _F, _F] + [_P] * 6,
+    "aanet_bn_act_apply_f32": [_P] * 6 + [_I, _P] + [_I] * 4 + [_P],
+    "aanet_bn_act_bwd_reduce_f32": [_P] * 5 + [_I] + [_P] * 3 + [_I] * 4 + [_P, ctypes.c_size_t, _P],
+    "aanet_bn_act_bwd_apply_f32": [_P] * 8 + [_I, _P, _P] + [_I] * 4 + [_P],
     "aanet_deconv2x_assemble_f32": [_P, _P, _P] + [_I] * 5 + [_P],
     "aanet_deconv2x_assemble_nhwc_f32": [_P, _P, _P] + [_I] * 5 + [_P],
     "aanet_concat_nhwc_f32": [_P, _P, _P] + [_I] * 5 + [_P],
@@ -91,6 +100,7 @@ _SIZE_FUNCTIONS = [
     ("aanet_conv2d_wgrad_workspace_size", [_I] * 11, ctypes.c_size_t),
     ("aanet_disp_loss_workspace_size", [_I] * 4, ctypes.c_size_t),
     ("aanet_disp_metrics_workspace_size", [_I] * 3, ctypes.c_size_t),
+    ("aanet_bn_act_workspace_size", [_I] * 5, ctypes.c_size_t),
     ("aanet_conv_weight_pack_split_bytes", [_I] * 5, _L),
     ("aanet_conv3x3s2_pack_bytes", [_I, _I], ctypes.c_size_t),
     ("aanet_conv3x3_grouped_pack_bytes", [_I, _I, _I], ctypes.c_size_t),

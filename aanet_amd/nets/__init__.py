@@ -2,6 +2,7 @@
 nets/estimation.py, nets/aggregation.py, nets/deform.py, nets/deform_conv/) and, around it, the
 feature extractors, refinement, warp, 3-D aggregators and the full AANet model."""
 from .aanet import AANet, set_train_up4  # noqa: F401
+from .train_bn import set_train_fused_bn  # noqa: F401
 from .aggregation import AdaptiveAggregation, AdaptiveAggregationModule  # noqa: F401
 from .aggregation3d import (GCNetAggregation, PSMNetBasicAggregation,  # noqa: F401
                             PSMNetHGAggregation, PSMNetHourglass, StereoNetAggregation)

@@ -498,6 +498,9 @@ class FusedSequential(FoldCacheMixin, nn.Sequential):
     def forward(self, x):
         if use_fused(self, x):
             return run_fused_chain(list(_leaves(self)), x)
+        if self.training and self.__dict__.get("aanet_fused_bn", False):  # nets.set_train_fused_bn
+            from .train_bn import run_sequential
+            return run_sequential(self, x)
         return super().forward(x)
 
 

@@ -36,7 +36,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from .._precision import fp32_convs
 from .. import ops
-from . import _fuse
+from . import _fuse, train_bn
 from ._fuse import FoldCacheMixin, use_fused
 
 
@@ -193,6 +193,13 @@ class PSMNetHourglass(FoldCacheMixin, nn.Module):
             else:
                 post = F.relu(_chain(self.conv5, out) + skip, inplace=True)
             return _chain(self.conv6, post, residual=out_residual), pre, post
+        if train_bn.enabled(self):  # nets.set_train_fused_bn: relu(BN(conv(.)) + skip) as one op
+            pre = train_bn.bn_act(self.conv2[1], self.conv2[0](self.conv1(x)), "relu", postsqu)
+            out = self.conv4(self.conv3(pre))
+            post = train_bn.bn_act(self.conv5[1], self.conv5[0](out), "relu",
+                                   pre if presqu is None else presqu)
+            out = self.conv6(post)
+            return out if out_residual is None else out + out_residual, pre, post
         pre = self.conv2(self.conv1(x))
         pre = F.relu(pre if postsqu is None else pre + postsqu, inplace=True)
         out = self.conv4(self.conv3(pre))

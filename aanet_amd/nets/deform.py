@@ -18,6 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from . import train_bn
 from ._fuse import (FoldCacheMixin, bn_affine, conv_bn_act, conv_bn_act_s2, folded,
                     halo_input_ok, offset_conv_eval, use_fused)
 from .deform_conv import DeformConv, ModulatedDeformConv
@@ -122,6 +123,8 @@ def _take_post(r, post):
 
 class _BottleneckBase(FoldCacheMixin, nn.Module):
     def _forward_ref(self, x):
+        if train_bn.enabled(self):  # nets.set_train_fused_bn
+            return train_bn.bottleneck_forward(self, x)
         identity = x
         out = self.conv1(x)
         out = self.bn1(out)

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 from ._fuse import (FusedSequential, conv_bn_act, conv_bn_act_s2, deconv2x_ok, deconv_bn_act,
                     engine_conv, halo_input_ok, use_fused)
 from .. import ops
+from . import train_bn
 from .deform import DeformConv2d
 from .._precision import fp32_convs
 
@@ -88,6 +89,9 @@ class BasicBlock(nn.Module):
             out = conv_bn_act(x, self.conv1, self.bn1, act)
             return conv_bn_act(out, self.conv2, self.bn2, act,
                                residual=_residual_src(self, x).contiguous())
+        if train_bn.enabled(self):  # nets.set_train_fused_bn
+            out = train_bn.bn_act(self.bn1, self.conv1(x), self.relu)
+            return train_bn.bn_act(self.bn2, self.conv2(out), self.relu, _residual_src(self, x))
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
         out += _residual_src(self, x)
@@ -278,6 +282,8 @@ class BasicConv(nn.Module):
             return deconv_bn_act(x, self.conv, self.bn if self.use_bn else None,
                                  "relu" if self.relu else None)
         x = self.conv(x)
+        if self.use_bn and train_bn.enabled(self):  # nets.set_train_fused_bn
+            return train_bn.bn_act(self.bn, x, "relu" if self.relu else None)
         if self.use_bn:
             x = self.bn(x)
         if self.relu:

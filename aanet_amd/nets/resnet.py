@@ -7,6 +7,7 @@ in the last conv's epilogue; DeformBottleneck's offset conv and DCN on the HIP k
 """
 import torch.nn as nn
 
+from . import train_bn
 from ._fuse import FusedSequential, conv_bn_act, use_fused
 from .deform import DeformBottleneck, _BottleneckBase
 from .._precision import fp32_convs
@@ -50,6 +51,9 @@ class BasicBlock(nn.Module):
         if use_fused(self, x) and isinstance(self.bn1, nn.BatchNorm2d):
             out = conv_bn_act(x, self.conv1, self.bn1, "relu")
             return conv_bn_act(out, self.conv2, self.bn2, "relu", residual=identity.contiguous())
+        if train_bn.enabled(self):  # nets.set_train_fused_bn
+            out = train_bn.bn_act(self.bn1, self.conv1(x), self.relu)
+            return train_bn.bn_act(self.bn2, self.conv2(out), self.relu, identity)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
         out += identity

@@ -4,6 +4,7 @@ Each op allocates its outputs with torch (caching allocator, device memory) and 
 torch's current HIP stream through ``_lib.call`` -- capturable into a HIP graph.
 """
 import collections
+import contextlib
 import ctypes
 
 import torch
@@ -1333,6 +1334,356 @@ def disp_metrics(pred, gt, mask, thresholds):
          B, H, W, nt, (ctypes.c_float * max(nt, 1))(*thresholds), ptr(values), ptr(count), ptr(ws),
          nbytes, stream_of(gt))
     return values, count
+
+
+# ------------------------------- training-mode BatchNorm + activation + residual (bn_act.hip) ---
+BN_ALGOS = {"auto": 0, "one_launch": 1, "split": 2}  # AANET_BN_* (include/aanet_mi355x.h)
+_BN_FORMS = {1: "one_launch", 2: "split"}
+BNActPlan = collections.namedtuple("BNActPlan", "status form splits elems_per_split")
+
+# Classes of calls at which the fused op measured slower than the torch chain by more than the
+# run-to-run spread (tools/bn_act_bench.py, profiles/bn_act_bench.txt); the module switch
+# (nets.set_train_fused_bn) sends them to torch (bn_act_slower_than_torch).
+#   "eager_small": launches issued eagerly (no HIP-graph capture under way) on tensors below
+#   BN_ACT_EAGER_MIN_ELEMS values.  There the step is bound by the host, and the op's Python and
+#   ctypes path costs more than the seven torch dispatches it replaces (forward + backward
+#   175-190 us against 115-140 us at the 2-D training shapes); from [4, 64, 24, 36, 72] (15.9 M
+#   values) on it is faster eagerly too (181 against 243 us), and as a HIP-graph replay it is
+#   faster at every measured shape (1.2x to 4.6x).
+BN_ACT_SLOWER_THAN_TORCH = frozenset({"eager_small"})
+BN_ACT_EAGER_MIN_ELEMS = 1 << 23
+
+
+_BN_CAPTURE_WARMUP = [0]
+
+
+@contextlib.contextmanager
+def bn_act_capture_warmup():
+    """Scope of the eager warm-up steps that precede a HIP-graph capture (Trainer.graph_step):
+    inside it calls are classed as the capture will class them, so that the warm-up runs -- and
+    warms the allocator and the kernels for -- the path that is captured."""
+    _BN_CAPTURE_WARMUP[0] += 1
+    try:
+        yield
+    finally:
+        _BN_CAPTURE_WARMUP[0] -= 1
+
+
+def bn_act_slower_than_torch(numel, capturing):
+    """Whether a call on `numel` values falls in a class of BN_ACT_SLOWER_THAN_TORCH; capturing:
+    a HIP-graph capture is under way on the current stream (or warmed up for:
+    bn_act_capture_warmup)."""
+    return ("eager_small" in BN_ACT_SLOWER_THAN_TORCH and not capturing
+            and not _BN_CAPTURE_WARMUP[0] and numel < BN_ACT_EAGER_MIN_ELEMS)
+
+
+def bn_act_plan(n, c, s, algo="auto", split_elems=0):
+    """aanet_bn_act_plan (host only) -> BNActPlan: status 0 with the form ("one_launch" /
+    "split"), the splits per channel and the values per split, or the status the launch would
+    return for these sizes (-1 invalid, -2 unsupported) and None members."""
+    if not all(-2 ** 31 <= int(v) < 2 ** 31 for v in (n, c, s, split_elems)):
+        return BNActPlan(_lib.EUNSUPPORTED, None, None, None)
+    form, splits, elems = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = _lib.lib().aanet_bn_act_plan(int(n), int(c), int(s), BN_ALGOS[algo], int(split_elems),
+                                      ctypes.byref(form), ctypes.byref(splits),
+                                      ctypes.byref(elems))
+    if rc != 0:
+        return BNActPlan(rc, None, None, None)
+    return BNActPlan(0, _BN_FORMS[form.value], splits.value, elems.value)
+
+
+def _bn_dims(x):
+    """x [N, C, S...] -> (N, C, S); torch's error for one value per channel in training."""
+    if x.dim() < 2:
+        raise ValueError(f"bn_act: expected an [N, C, ...] input, got {tuple(x.shape)}")
+    n, c = x.shape[0], x.shape[1]
+    s = 1
+    for v in x.shape[2:]:
+        s *= v
+    if n * s == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size "
+                         f"{x.size()}")
+    return n, c, s
+
+
+def _bn_workspace(x, n, c, s, algo, split_elems, *, stage=False):
+    """The split form's partials, from torch's allocator on the current stream ((None, 0) for the
+    one-launch form)."""
+    nbytes = _lib.lib().aanet_bn_act_workspace_size(n, c, s, BN_ALGOS[algo], split_elems)
+    if nbytes == 0:
+        if stage:
+            raise ValueError(f"bn_act: no split plan for {tuple(x.shape)}")
+        return None, 0
+    return torch.empty((nbytes,), device=x.device, dtype=torch.uint8), nbytes
+
+
+def _bn_check_params(c, dev, **named):
+    for name, t in named.items():
+        if t.shape != (c,) or t.device != dev:
+            raise ValueError(f"bn_act: {name} must be [{c}] on {dev}; it is {tuple(t.shape)} on "
+                             f"{t.device}")
+
+
+def _bn_check_counter(num_batches_tracked, dev):
+    t = num_batches_tracked
+    if t.dtype != torch.int64 or t.numel() != 1 or t.device != dev:
+        raise ValueError("bn_act: num_batches_tracked is one int64 on the input's device")
+
+
+def _bn_bump(*buffers):
+    """The kernels wrote these buffers: advance their version counters (host only, no launch), as
+    torch's own in-place update does -- the eval path's folded-BatchNorm caches key on them
+    (nets/_fuse.py)."""
+    for t in buffers:
+        torch.autograd.graph.increment_version(t)
+
+
+def bn_act_train(x, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps,
+                 act=None, residual=None, algo="auto", split_elems=0):
+    """aanet_bn_act_train_f32: y = act(weight * (x - mean) * invstd + bias [+ residual]) with this
+    batch's statistics -> (y, save_mean, save_invstd).  running_mean / running_var are updated
+    with `momentum` and num_batches_tracked advances by one, in the same launches.  act: None,
+    "relu" or "leaky" (0.2).  No autograd (BNActTrainFunction)."""
+    dev = require_gpu(x, weight, bias, running_mean, running_var, residual,
+                      names=("x", "weight", "bias", "running_mean", "running_var", "residual"))
+    n, c, s = _bn_dims(x)
+    _bn_check_params(c, dev, weight=weight, bias=bias, running_mean=running_mean,
+                     running_var=running_var)
+    _bn_check_counter(num_batches_tracked, dev)
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError("bn_act: residual must have the input's shape")
+    y = torch.empty_like(x)
+    save_mean = torch.empty((c,), device=dev, dtype=torch.float32)
+    save_invstd = torch.empty((c,), device=dev, dtype=torch.float32)
+    ws, nbytes = _bn_workspace(x, n, c, s, algo, split_elems)
+    call("aanet_bn_act_train_f32", ptr(x), ptr(residual), ptr(weight), ptr(bias),
+         ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), float(momentum),
+         float(eps), ACT[act], ptr(y), ptr(save_mean), ptr(save_invstd), n, c, s, BN_ALGOS[algo],
+         split_elems, ptr(ws), nbytes, stream_of(x))
+    _bn_bump(running_mean, running_var, num_batches_tracked)
+    return y, save_mean, save_invstd
+
+
+def bn_act_train_backward(grad_out, x, weight, save_mean, save_invstd, y=None, act=None,
+                          with_residual=False, algo="auto", split_elems=0):
+    """aanet_bn_act_train_bwd_f32 -> (grad_x, grad_weight, grad_bias, grad_residual or None).  y
+    (the forward's output) is needed with an activation only."""
+    if act is not None and y is None:
+        raise ValueError("bn_act_train_backward: the saved output is needed with an activation")
+    y = y if act is not None else None
+    dev = require_gpu(grad_out, x, weight, save_mean, save_invstd, y,
+                      names=("grad_out", "x", "weight", "save_mean", "save_invstd", "y"))
+    n, c, s = _bn_dims(x)
+    _bn_check_params(c, dev, weight=weight, save_mean=save_mean, save_invstd=save_invstd)
+    if grad_out.shape != x.shape or (y is not None and y.shape != x.shape):
+        raise ValueError("bn_act_train_backward: grad_out and y must have the input's shape")
+    gx = torch.empty_like(x)
+    gres = torch.empty_like(x) if with_residual else None
+    gw = torch.empty((c,), device=dev, dtype=torch.float32)
+    gb = torch.empty((c,), device=dev, dtype=torch.float32)
+    ws, nbytes = _bn_workspace(x, n, c, s, algo, split_elems)
+    call("aanet_bn_act_train_bwd_f32", ptr(grad_out), ptr(x), ptr(y), ptr(weight), ptr(save_mean),
+         ptr(save_invstd), ACT[act], ptr(gx), ptr(gres), ptr(gw), ptr(gb), n, c, s,
+         BN_ALGOS[algo], split_elems, ptr(ws), nbytes, stream_of(x))
+    return gx, gw, gb, gres
+
+
+def _bn_act_backward_torch(grad_out, x, weight, eps, y, act):
+    """bn_act_train_backward's formulas as torch ops, differentiable with respect to grad_out, x
+    and weight (the statistics are recomputed from x; the activation mask from the saved output
+    is piecewise constant) -> (grad_x, grad_weight, grad_bias, g)."""
+    dims = [0] + list(range(2, x.dim()))
+    shape = (1, -1) + (1,) * (x.dim() - 2)
+    g = grad_out
+    if act is not None:
+        g = torch.where(y > 0, grad_out, grad_out * (0.0 if act == "relu" else 0.2))
+    mean = x.mean(dims, keepdim=True)
+    invstd = torch.rsqrt(x.var(dims, unbiased=False, keepdim=True) + eps)
+    xhat = (x - mean) * invstd
+    gw, gb = (g * xhat).sum(dims), g.sum(dims)
+    count = x.numel() // x.shape[1]
+    gx = weight.view(shape) * invstd * (g - gb.view(shape) / count - xhat * gw.view(shape) / count)
+    return gx, gw, gb, g
+
+
+class BNActTrainFunction(Function):
+    """Training-mode BatchNorm with its activation and residual add as one op (bn_act.hip).
+    apply(x, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps, act,
+    residual, algo, split_elems) -> y.  Saves x, weight, save_mean, save_invstd, and y only with
+    an activation.  The HIP backward is once-differentiable; a backward that is itself recorded
+    (create_graph=True: double backward) runs the same formulas as torch ops on the saved
+    tensors instead (_bn_act_backward_torch)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, momentum,
+                eps, act=None, residual=None, algo="auto", split_elems=0):
+        x = x.contiguous()
+        residual = None if residual is None else residual.contiguous()
+        y, save_mean, save_invstd = bn_act_train(
+            x, weight.contiguous(), bias.contiguous(), running_mean, running_var,
+            num_batches_tracked, momentum, eps, act, residual, algo, split_elems)
+        ctx.cfg = (act, residual is not None, algo, split_elems)
+        ctx.eps = eps
+        ctx.save_for_backward(x, weight, save_mean, save_invstd, *((y,) if act is not None else ()))
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, weight, save_mean, save_invstd, *rest = ctx.saved_tensors
+        act, with_res, algo, split_elems = ctx.cfg
+        if torch.is_grad_enabled():  # this backward is being recorded: the differentiable form
+            gx, gw, gb, g = _bn_act_backward_torch(grad_out, x, weight, ctx.eps,
+                                                   rest[0] if rest else None, act)
+            return (gx, gw, gb) + (None,) * 6 + (g if with_res else None, None, None)
+        gx, gw, gb, gres = bn_act_train_backward(
+            grad_out.contiguous(), x, weight.contiguous(), save_mean, save_invstd,
+            rest[0] if rest else None, act, with_res and ctx.needs_input_grad[9], algo, split_elems)
+        return (gx, gw, gb) + (None,) * 6 + (gres, None, None)
+
+
+# ---- the split form's stages (SyncBatchNorm) ----
+def bn_act_stats(x, split_elems=0):
+    """aanet_bn_act_stats_f32 -> row [2C + 1] float64: this rank's mean [C], M2 [C], count."""
+    dev = require_gpu(x, names=("x",))
+    n, c = x.shape[0], x.shape[1]
+    s = x.numel() // max(n * c, 1)
+    row = torch.empty((2 * c + 1,), device=dev, dtype=torch.float64)
+    ws, nbytes = _bn_workspace(x, n, c, s, "split", split_elems, stage=True)
+    call("aanet_bn_act_stats_f32", ptr(x), n, c, s, split_elems, ptr(row), ptr(ws), nbytes,
+         stream_of(x))
+    return row
+
+
+def bn_act_finish(rows, running_mean, running_var, num_batches_tracked, momentum, eps):
+    """aanet_bn_act_finish_f32: rows [R, 2C + 1] float64 (bn_act_stats of every rank, in rank
+    order) -> (save_mean, save_invstd) of the whole batch; the running update and the counter."""
+    if rows.dtype != torch.float64 or rows.dim() != 2 or not rows.is_contiguous() \
+            or not rows.is_cuda or rows.shape[1] % 2 != 1:
+        raise ValueError("bn_act_finish: rows [R, 2C + 1] float64, contiguous, on the device")
+    c = (rows.shape[1] - 1) // 2
+    dev = require_gpu(running_mean, running_var, names=("running_mean", "running_var"))
+    _bn_check_params(c, rows.device, running_mean=running_mean, running_var=running_var)
+    _bn_check_counter(num_batches_tracked, dev)
+    save_mean = torch.empty((c,), device=dev, dtype=torch.float32)
+    save_invstd = torch.empty((c,), device=dev, dtype=torch.float32)
+    call("aanet_bn_act_finish_f32", ptr(rows), rows.shape[0], c, float(momentum), float(eps),
+         ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), ptr(save_mean),
+         ptr(save_invstd), stream_of(rows))
+    _bn_bump(running_mean, running_var, num_batches_tracked)
+    return save_mean, save_invstd
+
+
+def bn_act_apply(x, weight, bias, mean, invstd, act=None, residual=None, split_elems=0):
+    """aanet_bn_act_apply_f32: y from given statistics."""
+    dev = require_gpu(x, weight, bias, mean, invstd, residual,
+                      names=("x", "weight", "bias", "mean", "invstd", "residual"))
+    n, c = x.shape[0], x.shape[1]
+    s = x.numel() // max(n * c, 1)
+    _bn_check_params(c, dev, weight=weight, bias=bias, mean=mean, invstd=invstd)
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError("bn_act: residual must have the input's shape")
+    y = torch.empty_like(x)
+    call("aanet_bn_act_apply_f32", ptr(x), ptr(residual), ptr(weight), ptr(bias), ptr(mean),
+         ptr(invstd), ACT[act], ptr(y), n, c, s, split_elems, stream_of(x))
+    return y
+
+
+def bn_act_backward_reduce(grad_out, x, mean, invstd, y=None, act=None, split_elems=0):
+    """aanet_bn_act_bwd_reduce_f32 -> (sums [2C] float64: this rank's sum g, sum g * xhat;
+    grad_weight, grad_bias: the same local sums in fp32)."""
+    y = y if act is not None else None
+    dev = require_gpu(grad_out, x, mean, invstd, y, names=("grad_out", "x", "mean", "invstd", "y"))
+    n, c = x.shape[0], x.shape[1]
+    s = x.numel() // max(n * c, 1)
+    sums = torch.empty((2 * c,), device=dev, dtype=torch.float64)
+    gw = torch.empty((c,), device=dev, dtype=torch.float32)
+    gb = torch.empty((c,), device=dev, dtype=torch.float32)
+    ws, nbytes = _bn_workspace(x, n, c, s, "split", split_elems, stage=True)
+    call("aanet_bn_act_bwd_reduce_f32", ptr(grad_out), ptr(x), ptr(y), ptr(mean), ptr(invstd),
+         ACT[act], ptr(sums), ptr(gw), ptr(gb), n, c, s, split_elems, ptr(ws), nbytes,
+         stream_of(x))
+    return sums, gw, gb
+
+
+def bn_act_backward_apply(grad_out, x, weight, mean, invstd, sums, total_count, y=None, act=None,
+                          with_residual=False, split_elems=0):
+    """aanet_bn_act_bwd_apply_f32 -> (grad_x, grad_residual or None) with the sums over every
+    rank's batch [2C] float64 and their total count (a 0-dim float64 device tensor)."""
+    y = y if act is not None else None
+    require_gpu(grad_out, x, weight, mean, invstd, y,
+                names=("grad_out", "x", "weight", "mean", "invstd", "y"))
+    n, c = x.shape[0], x.shape[1]
+    s = x.numel() // max(n * c, 1)
+    if sums.dtype != torch.float64 or sums.numel() != 2 * c or not sums.is_contiguous() \
+            or total_count.dtype != torch.float64 or total_count.numel() != 1 \
+            or sums.device != x.device or total_count.device != x.device:
+        raise ValueError("bn_act_backward_apply: sums [2C] and total_count [] float64 on the device")
+    gx = torch.empty_like(x)
+    gres = torch.empty_like(x) if with_residual else None
+    call("aanet_bn_act_bwd_apply_f32", ptr(grad_out), ptr(x), ptr(y), ptr(weight), ptr(mean),
+         ptr(invstd), ptr(sums), ptr(total_count), ACT[act], ptr(gx), ptr(gres), n, c, s,
+         split_elems, stream_of(x))
+    return gx, gres
+
+
+class SyncBNActTrainFunction(Function):
+    """BNActTrainFunction across the ranks of a process group: this rank's statistics
+    (bn_act_stats), an all-gather of the rows -- the collective torch's SyncBatchNorm uses on the
+    backend --, the finish over the rows in rank order (unequal counts allowed), the apply.
+    Backward: this rank's sum g and sum g * xhat with the global statistics, one all-reduce of
+    [2C], then grad_x with the global count; grad_weight / grad_bias stay local sums, as in torch
+    (DDP averages them).  apply(x, weight, bias, running_mean, running_var, num_batches_tracked,
+    momentum, eps, act, residual, process_group) -> y.
+    Every rank must make the same calls: x and residual of any layout are made contiguous, and a
+    rank whose local batch is empty contributes a row with count 0 and zero sums.  With fewer
+    than 2 values per channel over all ranks the running statistics stay as they are (torch
+    raises there; the counts are device values).  Once-differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, momentum,
+                eps, act, residual, process_group):
+        import torch.distributed as dist
+        x = x.contiguous()
+        residual = None if residual is None else residual.contiguous()
+        weight, bias = weight.contiguous(), bias.contiguous()
+        empty = x.numel() == 0
+        row = torch.zeros((2 * x.shape[1] + 1,), device=x.device, dtype=torch.float64) if empty \
+            else bn_act_stats(x)
+        world = dist.get_world_size(process_group)
+        rows = torch.empty((world, row.numel()), device=x.device, dtype=torch.float64)
+        if dist.get_backend(process_group) != "gloo":
+            dist.all_gather_into_tensor(rows, row, process_group, async_op=False)
+        else:  # gloo has no all_gather_into_tensor (torch/nn/modules/_functions.py)
+            dist.all_gather(list(rows.unbind(0)), row, process_group, async_op=False)
+        save_mean, save_invstd = bn_act_finish(rows, running_mean, running_var,
+                                               num_batches_tracked, momentum, eps)
+        y = torch.empty_like(x) if empty else \
+            bn_act_apply(x, weight, bias, save_mean, save_invstd, act, residual)
+        ctx.cfg = (act, residual is not None, process_group)
+        ctx.save_for_backward(x, weight, save_mean, save_invstd, rows[:, -1].sum(),
+                              *((y,) if act is not None else ()))
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        import torch.distributed as dist
+        x, weight, save_mean, save_invstd, total, *rest = ctx.saved_tensors
+        act, with_res, process_group = ctx.cfg
+        y = rest[0] if rest else None
+        grad_out = grad_out.contiguous()
+        want_res = with_res and ctx.needs_input_grad[9]
+        if x.numel() == 0:  # an empty local batch: zero sums into the same all-reduce
+            sums = torch.zeros((2 * x.shape[1],), device=x.device, dtype=torch.float64)
+            dist.all_reduce(sums, dist.ReduceOp.SUM, process_group, async_op=False)
+            zero = torch.zeros_like(weight)
+            return (torch.empty_like(x), zero, zero.clone()) + (None,) * 6 + (
+                torch.empty_like(x) if want_res else None, None)
+        sums, gw, gb = bn_act_backward_reduce(grad_out, x, save_mean, save_invstd, y, act)
+        dist.all_reduce(sums, dist.ReduceOp.SUM, process_group, async_op=False)
+        gx, gres = bn_act_backward_apply(grad_out, x, weight, save_mean, save_invstd, sums, total,
+                                         y, act, want_res)
+        return (gx, gw, gb) + (None,) * 6 + (gres, None)
 
 
 DCN_BWD_ALGOS = {"auto": 0, "global": 1, "window": 2}  # AANET_DCN_BWD_* (include/aanet_mi355x.h)

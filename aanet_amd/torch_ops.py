@@ -272,6 +272,87 @@ def _(pred, gt, mask, thresholds):
     return gt.new_empty((2 + len(thresholds),)), gt.new_empty((), dtype=torch.int64)
 
 
+# ------------------------------------- training-mode BatchNorm + activation + residual ---
+def _bn_act_name(act: str):
+    if act not in ("none", "relu", "leaky"):
+        raise ValueError(f"bn_act_train: act is 'none', 'relu' or 'leaky', not {act!r}")
+    return None if act == "none" else act
+
+
+# The forward writes its running-statistics arguments, and torch.library.custom_op registers no
+# autograd formula for an op that mutates its inputs: the schema is defined directly, with a HIP
+# kernel and an Autograd-key implementation (a Function that redispatches below autograd).
+_bn_lib = torch.library.Library(_NS, "FRAGMENT")
+_bn_lib.define("bn_act_train(Tensor x, Tensor weight, Tensor bias, Tensor(a!) running_mean, "
+               "Tensor(b!) running_var, Tensor(c!) num_batches_tracked, float momentum, float eps, "
+               "str act, Tensor? residual) -> (Tensor, Tensor, Tensor)")
+
+
+def _bn_act_train_hip(x, weight, bias, running_mean, running_var, num_batches_tracked, momentum,
+                      eps, act, residual):
+    """ops.bn_act_train -> (y, save_mean, save_invstd); act: "none", "relu" or "leaky".  The
+    running statistics and the counter are updated in place."""
+    return ops.bn_act_train(x.contiguous(), weight.contiguous(), bias.contiguous(), running_mean,
+                            running_var, num_batches_tracked, momentum, eps, _bn_act_name(act),
+                            None if residual is None else residual.contiguous())
+
+
+_bn_lib.impl("bn_act_train", _bn_act_train_hip, "CUDA")
+
+
+@torch.library.register_fake(f"{_NS}::bn_act_train")
+def _(x, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps, act,
+      residual):
+    c = x.shape[1]
+    return (torch.empty_like(x, memory_format=torch.contiguous_format), x.new_empty((c,)),
+            x.new_empty((c,)))
+
+
+@torch.library.custom_op(f"{_NS}::bn_act_train_backward", mutates_args=(), device_types="cuda")
+def bn_act_train_backward(grad_out: Tensor, x: Tensor, weight: Tensor, save_mean: Tensor,
+                          save_invstd: Tensor, y: Optional[Tensor], act: str,
+                          with_residual: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """ops.bn_act_train_backward -> (grad_x, grad_weight, grad_bias, grad_residual; the last is
+    empty without a residual)."""
+    gx, gw, gb, gres = ops.bn_act_train_backward(
+        grad_out.contiguous(), x.contiguous(), weight.contiguous(), save_mean, save_invstd,
+        None if y is None else y.contiguous(), _bn_act_name(act), with_residual)
+    return gx, gw, gb, (gres if gres is not None else x.new_empty((0,)))
+
+
+@bn_act_train_backward.register_fake
+def _(grad_out, x, weight, save_mean, save_invstd, y, act, with_residual):
+    gx = torch.empty_like(x, memory_format=torch.contiguous_format)
+    return (gx, torch.empty_like(weight), torch.empty_like(weight),
+            torch.empty_like(gx) if with_residual else x.new_empty((0,)))
+
+
+class _BNActTrainOp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, num_batches_tracked, momentum,
+                eps, act, residual):
+        with torch._C._AutoDispatchBelowAutograd():
+            y, save_mean, save_invstd = torch.ops.aanet.bn_act_train(
+                x, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps,
+                act, residual)
+        ctx.act, ctx.with_residual = act, residual is not None
+        ctx.save_for_backward(x, weight, save_mean, save_invstd, *((y,) if act != "none" else ()))
+        ctx.mark_non_differentiable(save_mean, save_invstd)
+        return y, save_mean, save_invstd
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y, _grad_mean, _grad_invstd):
+        x, weight, save_mean, save_invstd, *rest = ctx.saved_tensors
+        gx, gw, gb, gres = bn_act_train_backward(grad_y, x, weight, save_mean, save_invstd,
+                                                 rest[0] if rest else None, ctx.act,
+                                                 ctx.with_residual)
+        return (gx, gw, gb) + (None,) * 6 + (gres if ctx.with_residual else None,)
+
+
+_bn_lib.impl("bn_act_train", lambda *args: _BNActTrainOp.apply(*args), "Autograd")
+
+
 OPS = ("mdcn_forward", "mdcn_backward", "corr_volume", "corr_volume_backward", "disp_regress",
        "disp_regress_backward", "disp_regress_up4", "disp_loss", "disp_loss_backward",
-       "disp_metrics", "disp_regress_up4_backward")
+       "disp_metrics", "disp_regress_up4_backward", "bn_act_train", "bn_act_train_backward")

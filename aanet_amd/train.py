@@ -31,7 +31,7 @@ import torch.nn.functional as F
 
 from . import ops
 from ._precision import CONV2D_TYPES, PinnedConv2d, fp32_scope
-from .nets import set_train_up4
+from .nets import set_train_fused_bn, set_train_up4
 from .nets._fuse import clear_fold_caches
 
 # model.py:98-107: pyramid weights by pyramid length
@@ -202,7 +202,7 @@ class Trainer:
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, accumulation_steps=1,
                  highest_loss_only=False, max_disp=192, engine_convs=None, capturable=False,
-                 fused_loss=False, fused_regress=False):
+                 fused_loss=False, fused_regress=False, fused_bn=False):
         """max_disp: the image-resolution disparity range of the valid mask (train.py --max_disp,
         default 192), NOT the cost-volume D.  engine_convs: run the plain convs on the HIP engine
         (use_engine_convs); default: when the model is on the GPU (measured round 5: the training
@@ -212,7 +212,8 @@ class Trainer:
         step and graph_step compute the loss with disparity_loss_fused instead of
         disparity_loss.  fused_regress: a model with a PSMNet aggregator upsamples inside the
         soft-argmin, forward and backward (nets.set_train_up4: no [B, 4D, 4H, 4W] volume is held
-        for the backward); other models are unaffected."""
+        for the backward); other models are unaffected.  fused_bn: the training-mode BatchNorms run
+        with their activation and residual add as one HIP op (nets.set_train_fused_bn)."""
         if engine_convs is None:
             params = list(model.parameters())
             engine_convs = bool(params) and all(p.is_cuda for p in params)
@@ -226,6 +227,9 @@ class Trainer:
         self.fused_regress = fused_regress
         if fused_regress:
             set_train_up4(model)
+        self.fused_bn = fused_bn
+        if fused_bn:
+            set_train_fused_bn(model)
         # fused Adam (one multi-tensor kernel per step) when every parameter is on the GPU: the
         # foreach form's capturable branch divides by 0-dim step tensors, which this torch build
         # runs as two broadcast kernels PER PARAMETER (~360 launches, ~2 ms of a 20 ms step);
@@ -272,7 +276,8 @@ class Trainer:
                         for v in st.values() if torch.is_tensor(v)}
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
+            # (the warm-up takes the fused BatchNorm wherever the capture will: fused_bn)
+            with torch.cuda.stream(side), ops.bn_act_capture_warmup():
                 for _ in range(warmup):
                     self.optimizer.zero_grad(set_to_none=True)
                     body()

@@ -609,6 +609,84 @@ int aanet_disp_metrics_f32(const float *pred, int pred_h, int pred_w, const floa
                            const float *thresholds, float *out, long *count, void *workspace,
                            size_t workspace_bytes, aanet_stream_t stream);
 
+/* Training-mode BatchNorm fused with its activation and residual add (bn_act.hip):
+ *   y = act(weight * (x - mean) * invstd + bias [+ residual]),  act: 0 none, 1 relu, 2 leaky(0.2)
+ * over x [n, c, s] (s = H*W or D*H*W; contiguous), mean and the biased variance taken per channel
+ * over the n*s values of this batch, invstd = 1 / sqrt(var + eps).  The same call writes
+ * save_mean [c] and save_invstd [c], updates running = (1 - momentum) * running + momentum * stat
+ * (the variance unbiased by n*s / (n*s - 1)) and adds 1 to *num_batches_tracked (device int64).
+ * residual may be NULL.  y may not alias x.
+ *
+ * Two forms, chosen from (n, c, s, algo, split_elems) alone; aanet_bn_act_plan (host only) says
+ * which: AANET_BN_ONE_LAUNCH -- one workgroup per channel reduces, then re-reads and writes, in
+ * one launch -- and AANET_BN_SPLIT -- c x splits workgroups write (sum, sum of squares) partials
+ * into `workspace` (device, aanet_bn_act_workspace_size bytes; 0 and NULL for the one-launch
+ * form), a finishing launch adds them in split order, an apply launch follows (backward:
+ * partials, then an apply launch whose workgroups each re-add their channel's partials in split
+ * order).  AANET_BN_AUTO takes the one-launch form up to AANET_BN_ONE_LAUNCH_MAX values per
+ * channel.  split_elems: values of a channel per split, rounded up to a multiple of 4; 0 =
+ * automatic.  Sums are double per thread, a fixed tree per workgroup and split order across
+ * workgroups: no atomics, bit-reproducible, a function of the shapes and the form only.
+ * 16-byte loads where s allows (any s works, also 1, 2, 3 and odd s).
+ * AANET_EINVAL: null pointers, sizes that are not positive, n*s < 2 (no variance to train on),
+ * more than 4096 splits.  AANET_EUNSUPPORTED: n*s beyond the 32-bit per-channel index.
+ * No allocation, no synchronisation: forward and backward capture into a HIP graph. */
+enum { AANET_BN_AUTO = 0, AANET_BN_ONE_LAUNCH = 1, AANET_BN_SPLIT = 2 };
+enum { AANET_BN_ONE_LAUNCH_MAX = 32768 };
+int aanet_bn_act_plan(int n, int c, int s, int algo, int split_elems, int *form, int *splits,
+                      int *elems_per_split);
+size_t aanet_bn_act_workspace_size(int n, int c, int s, int algo, int split_elems);
+int aanet_bn_act_train_f32(const float *x, const float *residual, const float *weight,
+                           const float *bias, float *running_mean, float *running_var,
+                           long *num_batches_tracked, float momentum, float eps, int act,
+                           float *y, float *save_mean, float *save_invstd, int n, int c, int s,
+                           int algo, int split_elems, void *workspace, size_t workspace_bytes,
+                           aanet_stream_t stream);
+/* Backward: with g = grad_out * act'(y) (from the saved output: y > 0 -> 1, else 0 for relu and
+ * 0.2 for leaky) and xhat = (x - save_mean) * save_invstd,
+ *   grad_x = weight * invstd * (g - mean(g) - xhat * mean(g * xhat)),
+ *   grad_weight = sum g * xhat, grad_bias = sum g, grad_residual = g (NULL: not wanted);
+ * all OVERWRITTEN.  y is read only with an activation (NULL otherwise). */
+int aanet_bn_act_train_bwd_f32(const float *grad_out, const float *x, const float *y,
+                               const float *weight, const float *save_mean,
+                               const float *save_invstd, int act, float *grad_x,
+                               float *grad_residual, float *grad_weight, float *grad_bias, int n,
+                               int c, int s, int algo, int split_elems, void *workspace,
+                               size_t workspace_bytes, aanet_stream_t stream);
+
+/* The split form's stages on their own, for SyncBatchNorm: each rank reduces its own batch, the
+ * ranks exchange rows, every rank finishes over all rows in the same order.  The workspace is
+ * aanet_bn_act_workspace_size(n, c, s, AANET_BN_SPLIT, split_elems) bytes; one rank may hold a
+ * single value per channel (n*s >= 1).
+ *   stats:  row (device, 2c + 1 doubles) = this rank's mean [c], M2 = sum (x - mean)^2 [c], count.
+ *   finish: rows [num_rows][2c + 1] merged in row order (pairwise update of Chan et al. in double;
+ *           unequal counts allowed, rows with count 0 skipped) -> save_mean, save_invstd, the
+ *           running update with the total count, the counter (both left as they are when the
+ *           total count is below 2: no unbiased variance; the counts are device values).
+ *   apply:  y from given mean / invstd.
+ *   bwd_reduce: sums (device, 2c doubles) = this rank's sum g [c], sum g * xhat [c] with the given
+ *           (global) mean / invstd; grad_weight / grad_bias = the same local sums.
+ *   bwd_apply: grad_x (and grad_residual) with sums over all ranks and *total_count (device). */
+int aanet_bn_act_stats_f32(const float *x, int n, int c, int s, int split_elems, double *row,
+                           void *workspace, size_t workspace_bytes, aanet_stream_t stream);
+int aanet_bn_act_finish_f32(const double *rows, int num_rows, int c, float momentum, float eps,
+                            float *running_mean, float *running_var, long *num_batches_tracked,
+                            float *save_mean, float *save_invstd, aanet_stream_t stream);
+int aanet_bn_act_apply_f32(const float *x, const float *residual, const float *weight,
+                           const float *bias, const float *mean, const float *invstd, int act,
+                           float *y, int n, int c, int s, int split_elems,
+                           aanet_stream_t stream);
+int aanet_bn_act_bwd_reduce_f32(const float *grad_out, const float *x, const float *y,
+                                const float *mean, const float *invstd, int act, double *sums,
+                                float *grad_weight, float *grad_bias, int n, int c, int s,
+                                int split_elems, void *workspace, size_t workspace_bytes,
+                                aanet_stream_t stream);
+int aanet_bn_act_bwd_apply_f32(const float *grad_out, const float *x, const float *y,
+                               const float *weight, const float *mean, const float *invstd,
+                               const double *sums, const double *total_count, int act,
+                               float *grad_x, float *grad_residual, int n, int c, int s,
+                               int split_elems, aanet_stream_t stream);
+
 /* deform_conv_cuda.cpp:571-685 (modulated_deform_conv_cuda_backward) + kernel.cu:635-767.
  * grad_x, grad_offset, grad_mask are OVERWRITTEN; grad_weight and grad_bias (may be NULL)
  * ACCUMULATE, as in the reference (cpp:660-671). */
